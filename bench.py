@@ -47,7 +47,22 @@ status; rank 0 prints the JSON line.  The N > 1 line carries a multi_gpu record:
 gather time of each launch (HIP events on the launch stream, max over ranks) and the same run with
 the other reserve_cus setting (0 / 32 CUs left free for the gather).
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+A plain run does what the headline figure needs and no more: set-up (scene, upload, one untimed
+counting launch per timed launch shape; at N > 1 the assembly calibration), the warm-up (and one
+untimed launch of the first timed launch's shape when --warmup is shorter than that launch), the
+--steps timed frames, the --dump-outputs files, the JSON line.  Every other record above --
+single_frame, tree_records, roofline (its two diagnostic counting launches), cpu_baseline, and at
+N > 1 multi_gpu.assembly_ab / reserve_cus_ab -- is measured only with --full, after the timed run,
+and is null in a plain run's line.
+
+--dump-outputs DIR (rank 0): what the last timed launch left with its caller, as float32 .npy:
+frame.npy, the last timed step's frame [H, W, 3], and launch_frames.npy, the same fixed seeded
+sample of pixels from every frame of that launch [frames, K, 3] (sample_pixels: row-major pixel
+indices from a generator seeded with DUMP_SEED).  A frame over its share of the 64 MB is such a
+sample of its pixels [K, 3] too.  The scenes and cameras are fixed-seed, so equal arguments give
+equal inputs in every run.
+
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 """
 import argparse
 import json
@@ -91,6 +106,10 @@ VALU_CLOCK_GHZ = 2.4
 VALU_CYCLES = {"b32": 2, "f64": 4, "trans64": 8}
 STRIPE_H = 16
 PIPE_REPS = 4   # single_frame.pipelined: passes over the single-frame views
+DUMP_SEED = 20240611           # --dump-outputs: the pixel samples' generator
+DUMP_FRAME_BYTES = 32 << 20    # frame.npy; launch_frames.npy gets 28 MB: under 64 MB in all
+DUMP_LAUNCH_BYTES = 28 << 20
+DUMP_LAUNCH_PIXELS = 16384     # pixels sampled from each frame of the last launch, at most
 
 
 def parse():
@@ -99,6 +118,14 @@ def parse():
     ap.add_argument("--steps", type=int, default=256)
     ap.add_argument("--warmup", type=int, default=128)
     ap.add_argument("--scene", default="office")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed run, also measure the records a plain run leaves null: single_frame, "
+                         "tree_records, roofline, cpu_baseline and, at N > 1, multi_gpu.assembly_ab / reserve_cus_ab "
+                         "(the options below that shape those records act only with --full)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="rank 0, after the timed run: DIR/frame.npy (the last timed step's frame) and "
+                         "DIR/launch_frames.npy (a fixed seeded pixel sample of every frame of the last timed "
+                         "launch), float32, under 64 MB in all")
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--spp", type=int, default=1, help="n: n*n stratified samples per pixel")
@@ -370,15 +397,22 @@ def main():
     rays_adaptive_local = 0
     # the single-frame records render frames cams[0 .. NS) one per launch (an animation: distinct views)
     NS = max(1, min(a.single_frames, F))
-    rays_frame0_local = rays_of(counts_of(NS)) / NS  # rays per frame of those frames
-    tst = launch_counts(F, rtamd.RT_FLAG_TRAVERSAL_STATS)   # canonical 2-wide walk of the reference tree
-    wst = launch_counts(F, rtamd.RT_FLAG_WIDE_STATS)        # the production kernel's own fetches
+    rays_frame0_local = 0.0
+    work_bytes_frame = fetch_bytes_frame = 0.0
+    if a.full:
+        rays_frame0_local = rays_of(counts_of(NS)) / NS  # rays per frame of those frames
+        tst = launch_counts(F, rtamd.RT_FLAG_TRAVERSAL_STATS)   # canonical 2-wide walk of the reference tree
+        wst = launch_counts(F, rtamd.RT_FLAG_WIDE_STATS)        # the production kernel's own fetches
+        # per frame, averaged over the F frames of a launch
+        work_bytes_frame = (64 * tst.node_visits + 48 * tst.tri_tests + 64 * tst.closest_hits) / F
+        fetch_bytes_frame = (128 * wst.node_visits + 80 * wst.tri_tests + 96 * wst.closest_hits) / F
     adaptive_info = None
     if batched_adaptive:   # untimed: rays of the adaptive passes (selection depends on the primary images)
         ast, nsel = adaptive_frames(prims[0], bufs, F, True, stream)
         rays_adaptive_local += n_full * rays_of(ast) + (rays_of(adaptive_frames(prims[0], bufs, rem, True, stream)[0])
                                                         if rem else 0)
-        rays_frame0_local += rays_of(adaptive_frames(prims[0], bufs, 1, True, stream)[0])
+        if a.full:
+            rays_frame0_local += rays_of(adaptive_frames(prims[0], bufs, 1, True, stream)[0])
         adaptive_info = {"pixels_supersampled_per_frame": round(nsel / F, 1), "subp": 4, "threshold": 0.02,
                          "rays_per_frame": round(rays_of(ast) / F, 1), "frames_per_launch": F}
     elif a.adaptive:
@@ -388,9 +422,6 @@ def main():
         rays_frame0_local += rays_of(ast)
         adaptive_info = {("pixels_supersampled" if n == 1 else "pixels_supersampled_rank0"): nsel, "subp": 4,
                          "threshold": 0.02, "rays": rays_of(ast)}
-    # per frame, averaged over the F frames of a launch
-    work_bytes_frame = (64 * tst.node_visits + 48 * tst.tri_tests + 64 * tst.closest_hits) / F
-    fetch_bytes_frame = (128 * wst.node_visits + 80 * wst.tri_tests + 96 * wst.closest_hits) / F
 
     if a.rank_shape:   # rank 0's stripes stay where they are rendered: no collective in this shape
         gathers = [lambda b: b] * S
@@ -516,14 +547,23 @@ def main():
         return float(tmax[0])
 
     stream_warm_frames = 0   # one-frame launches that only warmed a stream (counted below)
+    shape_warm_frames = 0    # frames of untimed launches of the timed launch shape (counted below)
 
     def timed_run(warm):
         """warm-up frames, then the timed run of a.steps frames: (seconds (max over ranks), mean
         launch ms, mean gather ms); the per-launch event lists are refilled."""
-        nonlocal stream_warm_frames
+        nonlocal stream_warm_frames, shape_warm_frames
         for lst in (starts, ends, launch_frames, gstarts, gends):
             lst.clear()
         run(warm, False)
+        # the timed launch shape has been launched before it is timed: a warm-up shorter than the
+        # first timed launch renders fewer frames per launch, so one untimed launch of that shape
+        # follows it (--steps 20 --warmup 5, five alternating runs each: 22.0 Grays/s without it, 22.6
+        # with it, 22.6 with --warmup 65; 22.2 when the roofline's counting launches preceded the run)
+        first = min(a.steps, per_launch_of(assembly))
+        if warm < first:
+            run(first, False)
+            shape_warm_frames += first
         # every stream the timed run uses has carried a launch before it: a stream's first launch
         # pays its hardware queue's set-up (r05zv: two 10-frame launches on two streams, the second
         # stream new, 10.1 ms against 8.0 ms of launch time)
@@ -579,6 +619,9 @@ def main():
     elapsed, kernel_ms_avg, gather_ms_avg = timed_run(a.warmup)
     frames_per_launch = float(np.mean(launch_frames))
     last_image = image
+    # --dump-outputs: the last timed launch's frames as its caller holds them now (the --full records
+    # below render into the same buffers)
+    dumped = dump_outputs(a.dump_outputs, last_image) if a.dump_outputs and rank == 0 else None
 
     def over_ranks(vals):
         """[max over ranks, rank 0's] of each value (N > 1)."""
@@ -603,14 +646,14 @@ def main():
                         "collective of its frames' stripes + rank 0's re-interleave (peer assembly: around the "
                         "fence all_reduce) -- includes waiting for the slowest rank's render; means over the "
                         "timed launches, then max over ranks"}
-        main_frames = last_image.clone() if rank == 0 else None   # for the assembly A/B's bit check
+        main_frames = last_image.clone() if rank == 0 and a.full else None   # for the assembly A/B's bit check
 
     # single-frame record: the reference's use, one frame per launch (mytracer_gpu.cu:59-81)
     # (NS consecutive views of the orbit, one per launch) in the natural tile order, then with the
     # library's default for consecutive one-frame launches on a stream: each launch ordered by the
     # per-tile costs of the launch two before (one untimed pass of the NS views first)
     single = None
-    if a.single_frames > 0 and not a.adaptive:
+    if a.full and a.single_frames > 0 and not a.adaptive:
         def single_record(flags):
             for lst in (starts, ends, launch_frames, gstarts, gends):
                 lst.clear()
@@ -648,8 +691,8 @@ def main():
     # same way, with each tree's upload / build seconds -- BASELINE config 2 names the reference's
     # median-split tree (mybvh.cpp:375-539, walked by intersectBVH_device, mytracer_gpu.cu:340-424)
     tree_records = None
-    if a.tree_record == "on" or (a.tree_record == "auto" and n == 1 and not a.adaptive
-                                 and host.triangle_count < (1 << 20)):
+    if a.full and (a.tree_record == "on" or (a.tree_record == "auto" and n == 1 and not a.adaptive
+                                             and host.triangle_count < (1 << 20))):
         tree_records = {}
         for tree in [t for t in ("reference", "sah", "sbvh") if t != a.tree]:
             tree_records[tree] = tree_record(host, dev, a, upload_opts, tree, cams, F, fbufs[0], stream,
@@ -662,9 +705,9 @@ def main():
     # N > 1: the same run with the other frame assembly (RCCL gather <-> peer stores + fence), and
     # the last launch's assembled frames compared bit for bit with the main run's (same views)
     peer_failed = bool(assembly_choice and assembly_choice.get("reason"))
-    if peer_failed:
+    if peer_failed and a.full:
         multi["assembly_ab"] = {"skipped": assembly_choice["reason"]}
-    elif multi is not None and (a.assembly_ab == "on" or (a.assembly_ab == "auto" and not a.adaptive)):
+    elif multi is not None and a.full and (a.assembly_ab == "on" or (a.assembly_ab == "auto" and not a.adaptive)):
         main_as = assembly
         assembly = "peer" if main_as == "gather" else "gather"
         el2, k2, g2 = timed_run(min(a.warmup, F))
@@ -689,7 +732,7 @@ def main():
     # N > 1: the same run with the other reserve_cus setting (0 <-> 32 CUs left free for the
     # gather), so every N > 1 line measures what the reservation costs the render and what it
     # gains the gather overlap -- same scene, same launches, pixels identical
-    if multi is not None and (a.reserve_ab == "on" or (a.reserve_ab == "auto" and not a.adaptive)):
+    if multi is not None and a.full and (a.reserve_ab == "on" or (a.reserve_ab == "auto" and not a.adaptive)):
         main_r = multi["reserve_cus"]
         other = 32 if main_r <= 0 else 0
         gpu.close()
@@ -731,7 +774,7 @@ def main():
         # (N > 1: the PMC summary of the rank shape -- rank 0's launches profiled on one GPU with
         # --rank-shape N -- so the fractions are per GPU, of rank 0's kernel)
         key = workload_key(a, shape_n)
-        pmc = pmc_per_frame(key, frames_per_launch)
+        pmc = pmc_per_frame(key, frames_per_launch) if a.full else None
         kernel_s = kernel_ms_avg * 1e-3
         roof = {"bound": "hbm", "achieved": None, "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": None,
                 "traffic": None}
@@ -765,10 +808,12 @@ def main():
                         "def": "128*wide_node_visits + 80*tri_tests + 96*closest_hits (production kernel's "
                                "4-wide diagnostic variant) / (64 B/clk x 256 CUs x 2.4 GHz)",
                         "peak_source": L1_PEAK_SOURCE},
-            "wave_cycles": pmc_wave_mix(key, frames_per_launch),
-            "valu_roof": pmc_valu_roof(key, frames_per_launch, kernel_s / frames_per_launch),
+            "wave_cycles": pmc_wave_mix(key, frames_per_launch) if a.full else None,
+            "valu_roof": pmc_valu_roof(key, frames_per_launch, kernel_s / frames_per_launch) if a.full else None,
         })
         roof["bound"], roof["bound_basis"] = binding_resource(roof)
+        if not a.full:   # its work and fetch bytes come from counting launches of their own
+            roof = None
         out = {
             "metric": f"Mrays/sec (primary+shadow+reflect), {workload_label(a, host.triangle_count)}",
             "value": round(mrays, 2),
@@ -777,6 +822,7 @@ def main():
             "steps": a.steps,
             "warmup": a.warmup,
             "ms_per_step": round(ms_per_step, 4),
+            "full": bool(a.full),
             # the render kernel's own time per frame (HIP events around each launch / its frames)
             "kernel_ms_per_frame": round(kernel_ms_avg / frames_per_launch, 4),
             "higher_is_better": True,
@@ -812,8 +858,8 @@ def main():
                 "upload_wall_s": round(upload_wall_s, 4),
                 # frames the production kernel rendered in this process (counting launches, warm-up,
                 # timed run, single-frame run): the divisor tools/pmc_summary.py uses for per-frame bytes
-                "production_frames_rendered": (F + rem + NS + a.warmup + a.steps + stream_warm_frames
-                                               + (3 * NS if single else 0)
+                "production_frames_rendered": (F + rem + a.warmup + a.steps + stream_warm_frames + shape_warm_frames
+                                               + (NS if a.full else 0) + (3 * NS if single else 0)
                                                + (2 * PIPE_REPS * NS if single and "pipelined" in single else 0)
                                                if not a.adaptive else None),
                 "device_scene_MB": round(gpu.device_bytes / 1e6, 1),
@@ -829,8 +875,9 @@ def main():
             "tree_records": tree_records,
             "roofline": roof,
             "cpu_baseline": None,
+            "dump_outputs": dumped,
         }
-        if n == 1 and not a.no_cpu_baseline:
+        if a.full and n == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(host, params, a)
         print(json.dumps(out), flush=True)
     if n > 1:
@@ -839,6 +886,38 @@ def main():
             peer.close()
         dist.barrier()
         dist.destroy_process_group()
+
+
+def sample_pixels(n_pixels, k):
+    """k of n_pixels pixel indices, ascending: the same ones in every run (DUMP_SEED)."""
+    if k >= n_pixels:
+        return np.arange(n_pixels)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n_pixels, size=k, replace=False))
+
+
+def dump_outputs(path, frames):
+    """--dump-outputs: `frames` is what the last timed launch left with its caller on rank 0, a
+    [nf, rows, W, 3] tensor on the device (rows = H, or this shard's rows with --rank-shape).  Writes
+    frame.npy, the last frame (a sample_pixels() sample [K, 3] when it exceeds DUMP_FRAME_BYTES), and
+    launch_frames.npy, sample_pixels() of every frame [nf, K, 3]; float32; returns what it wrote."""
+    out = Path(path)
+    out.mkdir(parents=True, exist_ok=True)
+    if frames.dim() == 3:
+        frames = frames[None]
+    nf, width, n_pixels = frames.shape[0], frames.shape[2], frames.shape[1] * frames.shape[2]
+    px = 4 * frames.shape[3]   # bytes per float32 pixel
+
+    def sample(t, k):   # [..., rows, W, C] -> [..., k, C]: only the sampled pixels are copied
+        y, x = np.divmod(sample_pixels(n_pixels, k), width)
+        return t[..., torch.as_tensor(y, device=t.device), torch.as_tensor(x, device=t.device), :]
+    last = frames[-1] if n_pixels * px <= DUMP_FRAME_BYTES else sample(frames[-1], DUMP_FRAME_BYTES // px)
+    each = sample(frames, min(DUMP_LAUNCH_PIXELS, n_pixels, DUMP_LAUNCH_BYTES // (px * nf)))
+    wrote = {}
+    for name, t in (("frame", last), ("launch_frames", each)):
+        arr = np.ascontiguousarray(t.float().cpu().numpy())
+        np.save(out / f"{name}.npy", arr)
+        wrote[f"{name}.npy"] = {"shape": list(arr.shape), "dtype": str(arr.dtype)}
+    return wrote
 
 
 def upload_options_for(a, n):

@@ -41,15 +41,16 @@ def expected_frames(w, h, frames, upto=None):
 @pytest.mark.parametrize("frames", [1, 8])
 def test_bench_json_contract_and_saved_frame(tmp_path, frames):
     out = tmp_path / "frame.npy"
-    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "8", "--warmup", "8", "--width", "320",
-                        "--height", "180", "--frames", str(frames), "--no-cpu-baseline", "--save", str(out)],
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--full", "--steps", "8", "--warmup", "8",
+                        "--width", "320", "--height", "180", "--frames", str(frames), "--no-cpu-baseline",
+                        "--save", str(out)],
                        capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads(r.stdout.strip().splitlines()[-1])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert k in d, k
-    assert d["n_gpus"] == 1 and d["steps"] == 8 and d["value"] > 0
+    assert d["n_gpus"] == 1 and d["steps"] == 8 and d["value"] > 0 and d["full"] is True
     assert d["config"]["frames_per_launch"] == frames
     rf = d["roofline"]
     assert rf["bound"] in ("hbm", "l1", "valu", "latency", "unmeasured") and rf["peak"] == 8000.0 and rf["kernel_ms_avg"] > 0
@@ -69,6 +70,43 @@ def test_bench_json_contract_and_saved_frame(tmp_path, frames):
     ref, rays = expected_frames(320, 180, frames)
     assert np.array_equal(np.load(out), ref)
     assert d["config"]["rays_per_frame"] == rays
+
+
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    # without --full: the headline fields and config only (the other records null), and --dump-outputs
+    # writes the last timed launch's frames: the last step's frame whole, a fixed pixel sample of each
+    # frame of the launch -- equal bit for bit to direct renders of the same views
+    import importlib.util
+
+    spec = importlib.util.spec_from_file_location("bench_mod", ROOT / "bench.py")
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    w, h, frames = 320, 180, 8
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "12", "--warmup", "4",
+                        "--width", str(w), "--height", str(h), "--frames", str(frames), "--dump-outputs", str(out)],
+                       capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads(r.stdout.strip().splitlines()[-1])
+    assert d["full"] is False and d["steps"] == 12 and d["warmup"] == 4
+    assert d["value"] > 0 and d["ms_per_step"] > 0 and d["unit"] == "Mrays/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "f64" and d["metric"].startswith("Mrays/sec")
+    for k in ("single_frame", "tree_records", "roofline", "cpu_baseline", "multi_gpu"):
+        assert d[k] is None, k
+    # 12 steps in launches of 8: the last timed launch rendered views 0..3 of the 8-view orbit
+    hs = rtamd.HostScene.generate("office")
+    hs.prepare()
+    dev = rtamd.DeviceScene(hs, 0)
+    p = hs.render_params(w, h, 1)
+    views = [dev.render(rtamd.camera_orbit(p, SWEEP * (f / (frames - 1) - 0.5)))[0] for f in range(4)]
+    frame, each = np.load(out / "frame.npy"), np.load(out / "launch_frames.npy")
+    assert frame.dtype == np.float32 and each.dtype == np.float32
+    assert sorted(q.name for q in out.iterdir()) == ["frame.npy", "launch_frames.npy"] == sorted(d["dump_outputs"])
+    assert np.array_equal(frame, views[-1])
+    idx = b.sample_pixels(w * h, b.DUMP_LAUNCH_PIXELS)
+    assert each.shape == (4, len(idx), 3) and len(idx) == 16384 and frame.nbytes + each.nbytes <= 64 << 20
+    for f in range(4):
+        assert np.array_equal(each[f], views[f].reshape(-1, 3)[idx]), f
 
 
 def test_bench_adaptive_pass_runs():
@@ -139,7 +177,7 @@ def test_bench_peer_assembly_two_ranks(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["RT_BENCH_DEVICE"] = "0"
     r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--dist-backend", "gloo",
-                        "--assembly", "peer", "--reserve-ab", "off", "--steps", "16", "--warmup", "8", "--frames", "8",
+                        "--full", "--assembly", "peer", "--reserve-ab", "off", "--steps", "16", "--warmup", "8", "--frames", "8",
                         "--width", "320", "--height", "180", "--no-cpu-baseline", "--save", str(out)],
                        capture_output=True, text=True, timeout=300, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -167,7 +205,7 @@ def test_bench_four_ranks_driver_shape(tmp_path):
     env = dict(os.environ, RT_BENCH_DEVICE="0")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4",
                         "--master-addr", "127.0.0.1", "--master-port", str(port), str(ROOT / "bench.py"),
-                        "--gpus", "4", "--dist-backend", "gloo", "--steps", "20", "--warmup", "5",
+                        "--gpus", "4", "--full", "--dist-backend", "gloo", "--steps", "20", "--warmup", "5",
                         "--width", "320", "--height", "180", "--no-cpu-baseline", "--save", str(out)],
                        capture_output=True, text=True, timeout=300, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-2000:]

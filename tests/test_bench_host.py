@@ -39,6 +39,38 @@ def test_valu_roof_from_committed_summary():
     assert b.pmc_valu_roof(dict(key, scene="nonexistent"), 128, 0.36e-3) is None
 
 
+def test_dump_outputs_sizes_and_samples(tmp_path):
+    # --dump-outputs: float32 files under 64 MB in all; a frame over its 32 MB share and the frames
+    # of the launch are fixed pixel samples (the same indices in every run), else the frame is whole
+    import numpy as np
+    import torch
+
+    b = _bench()
+    small = torch.arange(3 * 5 * 7 * 3, dtype=torch.float32).reshape(3, 5, 7, 3)
+    wrote = b.dump_outputs(tmp_path / "s", small)
+    frame, each = np.load(tmp_path / "s/frame.npy"), np.load(tmp_path / "s/launch_frames.npy")
+    assert np.array_equal(frame, small[-1].numpy()) and np.array_equal(each, small.reshape(3, 35, 3).numpy())
+    assert wrote == {"frame.npy": {"shape": [5, 7, 3], "dtype": "float32"},
+                     "launch_frames.npy": {"shape": [3, 35, 3], "dtype": "float32"}}
+    idx = b.sample_pixels(1000, 10)
+    assert len(set(idx)) == 10 and list(idx) == sorted(idx) and np.array_equal(idx, b.sample_pixels(1000, 10))
+    # two frames of 1800 x 1600 pixels (34.6 MB each): the last one sampled down to 32 MB
+    n_pixels = 1800 * 1600
+    big = (torch.arange(2 * n_pixels, dtype=torch.float32) % 65536).reshape(2, 1800, 1600, 1).expand(2, 1800, 1600, 3)
+    b.dump_outputs(tmp_path / "b", big)
+    frame, each = np.load(tmp_path / "b/frame.npy"), np.load(tmp_path / "b/launch_frames.npy")
+    k = b.DUMP_FRAME_BYTES // 12
+    assert frame.shape == (k, 3) and each.shape == (2, b.DUMP_LAUNCH_PIXELS, 3)
+    assert frame.dtype == each.dtype == np.float32 and frame.nbytes + each.nbytes <= 64 << 20
+    flat = big.reshape(2, n_pixels, 3).numpy()
+    assert np.array_equal(frame, flat[1][b.sample_pixels(n_pixels, k)])
+    assert np.array_equal(each, flat[:, b.sample_pixels(n_pixels, b.DUMP_LAUNCH_PIXELS)])
+    # a launch of 128 frames keeps its share too: fewer pixels per frame
+    many = torch.zeros((128, 300, 400, 3))
+    b.dump_outputs(tmp_path / "m", many)
+    assert np.load(tmp_path / "m/launch_frames.npy").nbytes <= b.DUMP_LAUNCH_BYTES
+
+
 def test_metric_names_the_workload():
     b = _bench()
     a = types.SimpleNamespace(scene="office", width=1920, height=1080, spp=1, adaptive=False)

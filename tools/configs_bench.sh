@@ -15,7 +15,7 @@ O=gpurun_out/configs_$TAG
 mkdir -p $O
 run() {   # name, timeout, bench args...
   local n=$1 t=$2; shift 2
-  timeout -k 10 $t python -u bench.py "$@" > $O/$n.json 2> $O/$n.err || { echo "config $n failed"; exit 1; }
+  timeout -k 10 $t python -u bench.py --full "$@" > $O/$n.json 2> $O/$n.err || { echo "config $n failed"; exit 1; }
   echo "config $n done"
 }
 run c1 300 --scene spheres --width 640 --height 480 --cpu-seconds 10

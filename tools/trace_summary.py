@@ -5,7 +5,8 @@ usage: python tools/trace_summary.py OUT.json PROF_DIR BENCH.json
 
 bench.py's production-kernel dispatches come in a fixed order: the counting launch of F frames
 (plus one of steps % F frames when F does not divide --steps), the counting launch of the NS
-single-frame views, the warm-up launches, the timed launches, then three runs of NS one-frame
+single-frame views, the warm-up launches (and one launch of the timed shape when the warm-up is
+shorter than the first timed launch), the timed launches, then three runs of NS one-frame
 launches: the natural-order record, an untimed pass in the library's default (cost) order, and
 the default-order single-frame record.  The summary averages the timed launches and each
 single-frame record separately, so each figure can be set beside the bench's own HIP-event
@@ -36,7 +37,7 @@ def main():
     F = int(bench["config"]["rays_breakdown_rank0_launch"]["frames"])
     n_timed = -(-steps // F)
     n_count = 1 + (1 if steps % F else 0) + 1
-    n_warm = -(-warm // F) if warm else 0
+    n_warm = (-(-warm // F) if warm else 0) + (1 if warm < min(steps, F) else 0)
     n_single = bench["single_frame"]["frames"] if bench.get("single_frame") else 0
     t0 = n_count + n_warm
     timed = dur[t0:t0 + n_timed]

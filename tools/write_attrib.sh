@@ -18,7 +18,7 @@ for spec in "$@"; do
     for kv in $(echo ${spec#*#} | tr ',' ' '); do opts="$opts --opt $kv"; done
     name=${name}_$(echo ${spec#*#} | tr ',=' '__')
   fi
-  B="python bench.py --no-cpu-baseline --tree-record off --single-frames 0 $ARGS $opts"
+  B="python bench.py --full --no-cpu-baseline --tree-record off --single-frames 0 $ARGS $opts"
   RTAMD_HIP_LIB=$PWD/$l timeout -k 10 300 $B > $O/wa_${TAG}_$name.json
   RTAMD_HIP_LIB=$PWD/$l timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/wa_${TAG}_${name}_w \
     -o run -- $B > $O/wa_${TAG}_${name}_w.log 2>&1
