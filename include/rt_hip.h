@@ -415,7 +415,13 @@ int rt_scene_status(const rt_scene* scene);
  * wave-level node / leaf iteration (summed), triangle tests in leaves of > 4,
  * node iterations served from the LDS treelet; word 31 = watchdog flag; words
  * [32,35) = global-node iterations with one node for the whole wave, distinct
- * nodes of global-node iterations (summed), leaf iterations with one record.
+ * nodes of global-node iterations (summed), leaf iterations with one record;
+ * words 35, 36 = any-hit triangle tests and those of the ray's own record (STATS
+ * flags); word 37 = shadow_rays_skipped, every launch: the shadow rays (counted
+ * in word 9) whose light faces away from a surface of a material with shininess
+ * > 0 and finite coefficients, all light colours finite, so that their light term
+ * is exactly 0 -- not traced by the production kernels; with a STATS or timeline
+ * flag they are traced and only counted.
  * Returns the number of words copied (at most 40). */
 int rt_debug_counters(rt_scene* scene, unsigned long long* out, int n);
 

@@ -20,6 +20,7 @@
 //  * Shading data is only touched once per closest hit: per-slot vertex /
 //    uv indices, face normals, vertex normals, uvs, texels, materials.
 #pragma once
+#include <cmath>
 #include <cstdint>
 
 namespace rtk {
@@ -87,9 +88,21 @@ struct alignas(16) GMat {
   int32_t tex_w;    // -1: none
   int32_t tex_h;
   int64_t tex_off;  // texel offset
-  int64_t pad;
+  int64_t flags;    // kMatZeroTerm (mat_flags, set at upload)
 };
 static_assert(sizeof(GMat) == 128, "GMat must be 128 bytes");
+
+// GMat::flags bit 0: a light whose Lambert factor max(0, n.l) is 0 adds exactly +-0 to this
+// material's light sum, whatever its shadow ray finds (lighting(), oracle/rt_oracle.c):
+// shininess > 0, so the highlight is pow(+0, shininess) = +0, and ks -- and kd, unless a texture
+// replaces it (texels are finite) -- are finite, so colour * (kd * 0 + ks * 0) is +-0 for a finite
+// light colour.  The kernel does not trace such a shadow ray.
+constexpr int64_t kMatZeroTerm = 1;
+inline int64_t mat_flags(const GMat& G) {
+  bool fin = G.shininess > 0.0;
+  for (int k = 0; k < 3; ++k) fin = fin && std::isfinite(G.ks[k]) && (G.tex_w > 0 || std::isfinite(G.kd[k]));
+  return fin ? kMatZeroTerm : 0;
+}
 
 // Analytic primitive (opt-in, rt_scene_set_analytic): spheres first, then planes, each in
 // scene order -- the order intersect_scene tests them (oracle/rt_oracle.c intersect_scene).

@@ -180,6 +180,7 @@ enum : int {
   CD_FETCH_CYCLES, CD_OUTER_ITERS, CD_TRAV_ROUNDS, CD_TRAV_ROUND_LANES, CD_SPILLS, CD_NODE_LINES,
   CD_LEAF_LINES, CD_BIG_LEAF_TESTS, CD_NODE_LDS_ITERS, CD_GUARD = 31,   // CD_GUARD: a wave hit the iteration guard
   CD_GNODE_UNIFORM = 32, CD_GNODE_DISTINCT, CD_LEAF_UNIFORM, CD_ANYHIT_TRIS, CD_OWN_TRIS,
+  CD_ZERO_TERM,   // shadow rays whose light term is exactly 0: not traced (diagnostic variants: traced, counted)
   CT_ORDER_JOBS = 39   // cost-ordered launches: order / zeroing jobs claimed by blocks that finished
 };
 // Watchdogs (never reached by a correct kernel): the persistent loop, and the wave-level
@@ -257,7 +258,7 @@ struct KParams {
   const GMat* mats;
   unsigned long long* ctr;
   unsigned long long* heads;  // work head h at heads[h * kHeadStride]
-  unsigned long long* wctr;   // per wave {primary, shadow, reflection, 0} rays (plain stores at exit)
+  unsigned long long* wctr;   // per wave {primary, shadow, reflection, zero-term shadow} rays (plain stores at exit)
   double* pstate;       // path state, [nslots / 64][kRegions][64 lanes][4] fp64
   uint32_t* spill;      // [stack_words][nslots] traversal-stack entries below the LDS ring
   unsigned long long* wavelog;  // STATS: per wave {start, last refill, end, pixels} (s_memrealtime)
@@ -272,6 +273,7 @@ struct KParams {
   double root_lo[3], root_hi[3];
   int W, H;
   int n_lights, max_depth;
+  int zero_term_lights;     // kMatZeroTerm if every light colour of this launch is finite, else 0
   double bg[3], amb[3];
   int spp_n;
   // sample groups (spp > 1, rt_upload_options.spp_lanes): a pixel's samples run on G = 2^group_log
@@ -781,6 +783,7 @@ __global__ void __launch_bounds__(kBlock, kWavesPerEU * 256 / kBlock) render_ker
   int want = 0;           // owner: extra rays it would lend lanes for
   uint32_t htask = kTaskNone;   // helper: its task word
   unsigned c_primary = 0, c_shadow = 0, c_refl = 0, c_hits = 0;
+  unsigned n_zero_term = 0;   // wave-uniform: zero-term shadow rays of this wave (TRAVERSE phase)
   unsigned long long c_nodes = 0, c_tris = 0;
   unsigned long long d_node_it = 0, d_node_ln = 0, d_leaf_it = 0, d_leaf_ln = 0;
   unsigned long long d_trav = 0, d_shade = 0, d_fetch = 0, d_outer = 0, d_round_it = 0, d_round_ln = 0;
@@ -1052,6 +1055,7 @@ __global__ void __launch_bounds__(kBlock, kWavesPerEU * 256 / kBlock) render_ker
       D3 ro = d3(lds_d[0 * kBlock + src], lds_d[1 * kBlock + src], lds_d[2 * kBlock + src]);
       D3 rd = d3(lds_d[3 * kBlock + src], lds_d[4 * kBlock + src], lds_d[5 * kBlock + src]);
       double tlim = lds_d[6 * kBlock + src];
+      bool zero_term = false;   // a shadow ray whose light term is exactly +-0 (below)
       if (anyhit) {
         // a shadow ray (mytracer.cpp:589-600) for light j of the owner's bounce, derived from the
         // closest-hit ray and hit distance kept in the owner's slot: the same operations, in the
@@ -1061,6 +1065,14 @@ __global__ void __launch_bounds__(kBlock, kWavesPerEU * 256 / kBlock) render_ker
         const D3 to_l = sub(light_of(j).pos, hp);
         double nl;   // |to_l|: the light distance, the same sqrt as the normalisation's
         const D3 l = nrm_n(to_l, nl);
+        // zero-term ray: the owner's batch is eligible (launch_batch: bit 0 of its
+        // visibility word) and the light is not in front of the surface, so contrib_of's Lambert
+        // factor max(0, n.l) -- the same hp, l and normal (the owner's aux words), the same
+        // operations -- is 0 (a NaN dot too) and the light adds +-0 to the sum, occluded or not
+        if (lvis[src] & 1u) {
+          const D3 hn = d3(lds_d[7 * kBlock + src], lds_d[8 * kBlock + src], lds_d[9 * kBlock + src]);
+          zero_term = !(dot(hn, l) > 0.0);
+        }
         ro = add(hp, scl(1e-4, l));
         rd = nrm(l);
         tlim = nl;
@@ -1082,14 +1094,20 @@ __global__ void __launch_bounds__(kBlock, kWavesPerEU * 256 / kBlock) render_ker
       if (anyhit) own = (state == ST_SHADOW) ? own_rec : __shfl(own_rec, (int)(htask & 63u));
       best = kNoHit;
       best_slot = kNoHit;
-      shadow_hit = false;
+      // a zero-term ray is not traced: it reports "occluded" at once (the owner's own ray through
+      // shadow_hit, a helper's through its visibility bit), so SHADE skips that light's term as it
+      // does an occluded light's.  The ray stays counted where it was issued (c_shadow); the number
+      // not traced is wave-uniform (one ballot).  The diagnostic variants trace every ray -- the
+      // oracle pins their node and triangle counts -- and only count the marked ones.
+      n_zero_term += (unsigned)__popcll(wballot(zero_term));
+      shadow_hit = !STATS && !TL && zero_term;
       uint32_t cur = kDone;
       double t_off = 0.0;
       // analytic primitives first, in scene order (oracle/rt_oracle.c intersect_scene /
       // shadowed): a hit sets the running best with slot -1, so only a strictly closer
       // triangle replaces it; a shadow ray they block skips the BVH.
       for (int k = 0; k < P.n_prims; ++k) {
-        if (!busy) break;
+        if (!busy || shadow_hit) break;
         const double t = prim_hit(P.prims[k], ro, rd);
         if (t < tlim) {
           if (anyhit) { shadow_hit = true; break; }
@@ -1649,10 +1667,11 @@ __global__ void __launch_bounds__(kBlock, kWavesPerEU * 256 / kBlock) render_ker
       // own shadow ray for light `light`; the rest of the bounce is offered to idle lanes
       // (the ray itself is derived at the start of the next traversal from the slot's closest-hit
       // ray and distance)
-      auto launch_batch = [&](double mirror_) {
+      auto launch_batch = [&](double mirror_, const GMat& M_) {
         c_shadow++;
         state = ST_SHADOW;
-        lvis[threadIdx.x] = 0u;
+        // bit 0 (no helper's: theirs are 1..31): this batch's zero-term rays need no trace (TRAVERSE)
+        lvis[threadIdx.x] = (uint32_t)M_.flags & (uint32_t)P.zero_term_lights;
         batch_end = light + 1;
         refl_h = -1;
         // extra lights of this batch, then the reflection ray once the batch covers every light
@@ -1683,7 +1702,7 @@ __global__ void __launch_bounds__(kBlock, kWavesPerEU * 256 / kBlock) render_ker
         light = batch_end;
         if (light < P.n_lights) {
           STV(R_LACC, lacc);
-          launch_batch(mirror);
+          launch_batch(mirror, M);
         } else {   // bounce complete (subtrace, mytracer.cpp:546-555)
           D3 s0 = d3(0, 0, 0);
           double w = 1.0;
@@ -1785,7 +1804,7 @@ __global__ void __launch_bounds__(kBlock, kWavesPerEU * 256 / kBlock) render_ker
             ST_HN(hn);
             *R.tlim = thit;   // the slot keeps the closest-hit ray and its distance
             if (M.tex_w > 0) STV(R_HD, hdiff);
-            launch_batch(mirror);
+            launch_batch(mirror, M);
           } else {
             for (int j = 0; j < P.n_lights; ++j) lacc = add(lacc, contrib_of(j, hp, hn, hview, hdiff, M));
             D3 s0 = d3(0, 0, 0);
@@ -1943,7 +1962,7 @@ __global__ void __launch_bounds__(kBlock, kWavesPerEU * 256 / kBlock) render_ker
   if (lane == 0) {
     // plain stores to this wave's slot (summed by the host): no contended atomics at exit
     unsigned long long* wc = P.wctr + 4 * ((size_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6));
-    wc[0] = s0; wc[1] = s1; wc[2] = s2; wc[3] = 0;
+    wc[0] = s0; wc[1] = s1; wc[2] = s2; wc[3] = n_zero_term;
     if (STATS) {
       atomicAdd(&P.ctr[CS_NODES], s3);
       atomicAdd(&P.ctr[CS_TRIS], s4);
@@ -2601,6 +2620,7 @@ int read_counters(const LaunchCtx& C, unsigned long long* c) {
       c[CS_PRIMARY] += w[i];
       c[CS_SHADOW] += w[i + 1];
       c[CS_REFLECT] += w[i + 2];
+      c[CD_ZERO_TERM] += w[i + 3];
     }
   }
   return RT_OK;
@@ -2929,10 +2949,15 @@ int launch_render(rt_scene* sc, const rt_render_params* p, int n_frames, void* c
     fd[f].out = outs[f];
   }
   double* ld = reinterpret_cast<double*>(C.h_ctl + lights_at);
+  bool finite_lights = true;   // a non-finite colour times a zero light term is NaN: then every shadow ray is traced
   for (int i = 0; i < p->n_lights; ++i) {
     const rt_light* L = rt_params_light(p, i);
-    for (int k = 0; k < 3; ++k) { ld[6 * i + k] = L->position[k]; ld[6 * i + 3 + k] = L->color[k]; }
+    for (int k = 0; k < 3; ++k) {
+      ld[6 * i + k] = L->position[k]; ld[6 * i + 3 + k] = L->color[k];
+      finite_lights = finite_lights && std::isfinite(L->color[k]);
+    }
   }
+  P.zero_term_lights = finite_lights ? (int)kMatZeroTerm : 0;
   HIP_TRY(hipMemcpyAsync(C.d_ctr, C.h_ctl, ctl_bytes, hipMemcpyHostToDevice, st));
   if (v == 3) {   // round timeline: zeroed, so unused records read as t = 0
     const size_t tb = sc->nslots / 64 * kTlCap * kTlWords * sizeof(unsigned long long);
@@ -3481,6 +3506,7 @@ int rt_scene_set_analytic(rt_scene* sc, const rt_sphere* spheres, int n_spheres,
     G.shadowable = m.shadowable;
     G.draw_mode = RT_DRAW_FLAT;
     G.tex_w = -1;
+    G.flags = mat_flags(G);
     mats.push_back(G);
     return (int)mats.size() - 1;
   };

@@ -1229,6 +1229,7 @@ int build_image(const rt_scene_soa* s, const rt_bvh_soa* b, const rt_upload_opti
     G.tex_w = s->mesh_tex_width[m] > 0 ? s->mesh_tex_width[m] : -1;
     G.tex_h = s->mesh_tex_height[m];
     G.tex_off = s->mesh_tex_offset[m];
+    G.flags = mat_flags(G);
   }
   I.tu.assign(s->tex_u, s->tex_u + s->n_tex_coords);
   I.tv.assign(s->tex_v, s->tex_v + s->n_tex_coords);
