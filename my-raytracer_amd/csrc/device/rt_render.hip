@@ -23,7 +23,9 @@
 //     compiled with fp-contract off, so hits are bit-identical to the oracle;
 //   * rays live in LDS slots (fp64 origin / direction / t-limit + 3 aux words
 //     holding the hit's barycentrics or the bounce normal); idle lanes are lent
-//     to owners for their extra shadow rays and reflection ray (fan-out);
+//     to owners for their extra shadow rays and reflection ray (fan-out), and the
+//     shadow rays no lane was idle for are traced by the owner itself in further
+//     passes of the same traversal phase (one batch per bounce);
 //   * work distribution: persistent workgroups pull 8x8 pixel tiles from 8
 //     work heads on separate cache lines, one per XCD group, refilled per wave
 //     with a single atomic when >= kRefill lanes are idle; several frames per
@@ -67,6 +69,13 @@ constexpr int kGroups = 8;          // work heads (XCD groups)
 #define RT_REFILL 16
 #endif
 constexpr int kRefill = RT_REFILL;  // refill a wave when this many lanes are idle (8 / 32: -1.1 / -1.0 %, r06y)
+// Phase-gated refill: a wave claims work only while none of its lanes owns a shadow
+// batch about to be traced (or none is busy), so the pixels of one refill stay in phase -- closest-hit
+// and shadow iterations alternate for the whole wave, and the later TRAVERSE passes run full.
+#ifndef RT_REFILL_GATE
+#define RT_REFILL_GATE 0
+#endif
+constexpr bool kRefillGate = RT_REFILL_GATE != 0;
 constexpr int kCtrWords = 40;       // [8,16) stats (STATS variants), [16,40) diagnostics (31: guard)
 // Traversal stack: the top kShortStack entries live in an LDS ring (slot i & kStackMask),
 // deeper entries spill to a per-lane global array.  Bounds LDS per block independently
@@ -99,7 +108,10 @@ static_assert((kShortStack & kStackMask) == 0, "the stack ring must be a power o
 // Lane states.  Owners carry a pixel (CLOSEST: closest-hit ray in flight; SHADOW: a
 // batch of shadow rays in flight).  Idle lanes (FETCH / DONE) may be lent to an
 // owner of the same wave for one round (HSHADOW / HCLOSEST): they trace one of its
-// extra shadow rays or its reflection ray, so a bounce costs one round, not 1 + lights.
+// extra shadow rays or its reflection ray.  The lights of a batch that found no helper are
+// traced by the owner in later passes of the same TRAVERSE phase, so a bounce costs one
+// iteration of the persistent loop for its closest-hit ray and one for all its shadow rays
+// (up to 1 + kBatchExtra lights), not 1 + lights.
 // PARKED (sample groups, spp > 1): the lane's sample is finished and its colour waits in the lane's
 // slot for its group's ordered sum (below); a parked lane is neither busy nor idle.
 // a tile's pixels claimed in Morton order (RT_TILE_ROW_ORDER: row order): a partial refill's run of
@@ -118,8 +130,15 @@ constexpr uint32_t kTaskNone = 0xffffffffu;
 constexpr uint32_t kTaskRefl = 0x80000000u;
 static_assert(RT_LIGHTS_LIMIT <= (1 << 20), "light index must fit the task word");
 // a bounce's shadow rays go out in batches of at most 1 + kBatchExtra lights (the owner's
-// own ray + one helper per extra light): the helpers' occlusion bits fit one LDS word
+// first ray + one helper, or one later pass of the owner, per extra light): the extra lights'
+// occlusion bits fit one LDS word (bit light - batch start; bit 0 is the zero-term flag)
 constexpr int kBatchExtra = 31;
+// the owner's batch word: end of the batch's light range | lights of it that helpers took << kHelpShift
+// (the helpers take the lights right after the owner's first; the owner traces the rest itself, one
+// per pass of the TRAVERSE phase)
+constexpr int kHelpShift = 24;
+constexpr int kEndMask = (1 << kHelpShift) - 1;
+static_assert(RT_LIGHTS_LIMIT < (1 << kHelpShift), "light index must fit the batch word");
 
 // Orders LDS traffic between lanes of one wave: LDS executes a wave's operations in
 // issue order, so it suffices to stop the compiler from moving memory operations
@@ -778,7 +797,7 @@ __global__ void __launch_bounds__(kBlock, kWavesPerEU * 256 / kBlock) render_ker
   int best_slot = kNoHit;   // its reference slot (tie-break key)
   double thit = DBL_MAX;
   bool shadow_hit = false;
-  int batch_end = 0;      // owner: lights [light, batch_end) in flight
+  int batch_end = 0;      // owner: lights [light, batch_end & kEndMask) in flight | helper-traced ones << kHelpShift
   int refl_h = -1;        // owner: thread tracing its reflection ray this round (-1: none)
   int want = 0;           // owner: extra rays it would lend lanes for
   uint32_t htask = kTaskNone;   // helper: its task word
@@ -931,7 +950,8 @@ __global__ void __launch_bounds__(kBlock, kWavesPerEU * 256 / kBlock) render_ker
     // lanes that claim a work item: every idle lane, or (sample groups) the first lane of every idle
     // group, which claims a pixel for its G lanes
     unsigned long long m_claim = group_log ? full_groups(m_fetch) : m_fetch;
-    while (m_claim && (group_log || __popcll(m_fetch) >= kRefill || m_busy == 0) && heads_left > 0) {
+    const bool gate_open = !kRefillGate || m_busy == 0 || wballot(state == ST_SHADOW) == 0;   // wave-uniform
+    while (m_claim && gate_open && (group_log || __popcll(m_fetch) >= kRefill || m_busy == 0) && heads_left > 0) {
       const long long g0 = (n_tiles * head / kGroups) * 64;
       const long long g1 = (n_tiles * (head + 1) / kGroups) * 64;
       const int cnt = __popcll(m_claim);
@@ -1048,10 +1068,23 @@ __global__ void __launch_bounds__(kBlock, kWavesPerEU * 256 / kBlock) render_ker
       wave_lds_sync();
     }
     // ================= TRAVERSE phase =================
-    {
-      const bool anyhit = (state == ST_SHADOW || state == ST_HSHADOW);
+    // A wave-uniform loop of passes.  Pass 0 traces every busy lane's ray: closest-hit rays, helpers'
+    // rays and every shadow batch's first light.  Pass kp >= 1 traces, for the owners of a shadow
+    // batch only, the kp-th light of the batch that no helper took, until no owner has a light left:
+    // a bounce's shadow rays all finish in this one phase, whether idle lanes were there to help or
+    // not, and nothing between two passes but the test for another runs.  The first light's answer
+    // stays in shadow_hit, the later ones set the owner's visibility bits, as helpers do.  Lanes
+    // without a ray in a later pass keep their pass-0 result: shadow_hit in a wave mask (sh0), a
+    // closest hit in the lane's slot and its (idle) first ring entry.
+    unsigned long long sh0 = 0ull;   // wave-uniform: the lanes with shadow_hit after pass 0
+    int kp = 0;                      // wave-uniform: the pass
+    for (;; ++kp) {
+      // this lane traces a ray in this pass
+      const bool act = kp == 0 ? busy
+                               : (state == ST_SHADOW && light + (batch_end >> kHelpShift) + kp < (batch_end & kEndMask));
+      const bool anyhit = act && (state == ST_SHADOW || state == ST_HSHADOW);
       // helpers read their owner's slot (its closest-hit ray and hit distance)
-      const int src = (state >= ST_HSHADOW) ? wbase + (int)(htask & 63u) : (int)threadIdx.x;
+      const int src = (act && state >= ST_HSHADOW) ? wbase + (int)(htask & 63u) : (int)threadIdx.x;
       D3 ro = d3(lds_d[0 * kBlock + src], lds_d[1 * kBlock + src], lds_d[2 * kBlock + src]);
       D3 rd = d3(lds_d[3 * kBlock + src], lds_d[4 * kBlock + src], lds_d[5 * kBlock + src]);
       double tlim = lds_d[6 * kBlock + src];
@@ -1060,7 +1093,8 @@ __global__ void __launch_bounds__(kBlock, kWavesPerEU * 256 / kBlock) render_ker
         // a shadow ray (mytracer.cpp:589-600) for light j of the owner's bounce, derived from the
         // closest-hit ray and hit distance kept in the owner's slot: the same operations, in the
         // same order, as the emission of an explicit ray (emit_ray normalises the direction again)
-        const int j = (state == ST_SHADOW) ? light : (int)((htask >> 11) & 0xFFFFFu);
+        const int j = (state == ST_SHADOW) ? light + (kp > 0 ? (batch_end >> kHelpShift) + kp : 0)
+                                           : (int)((htask >> 11) & 0xFFFFFu);
         const D3 hp = add(ro, scl(tlim, rd));
         const D3 to_l = sub(light_of(j).pos, hp);
         double nl;   // |to_l|: the light distance, the same sqrt as the normalisation's
@@ -1076,7 +1110,7 @@ __global__ void __launch_bounds__(kBlock, kWavesPerEU * 256 / kBlock) render_ker
         ro = add(hp, scl(1e-4, l));
         rd = nrm(l);
         tlim = nl;
-      } else if (state == ST_HCLOSEST) {
+      } else if (act && state == ST_HCLOSEST) {
         // the owner's reflection ray (mytracer.cpp:547-552), from its hit and its normal (the
         // owner's aux words); kept in this helper's slot, from which the owner takes it over
         const D3 hp = add(ro, scl(tlim, rd));
@@ -1107,7 +1141,7 @@ __global__ void __launch_bounds__(kBlock, kWavesPerEU * 256 / kBlock) render_ker
       // shadowed): a hit sets the running best with slot -1, so only a strictly closer
       // triangle replaces it; a shadow ray they block skips the BVH.
       for (int k = 0; k < P.n_prims; ++k) {
-        if (!busy || shadow_hit) break;
+        if (!act || shadow_hit) break;
         const double t = prim_hit(P.prims[k], ro, rd);
         if (t < tlim) {
           if (anyhit) { shadow_hit = true; break; }
@@ -1116,23 +1150,29 @@ __global__ void __launch_bounds__(kBlock, kWavesPerEU * 256 / kBlock) render_ker
           best_slot = -1;
         }
       }
-      if (busy && P.n_gnodes > 0 && !shadow_hit) {   // conservative fp32 box ray (oracle/rt_oracle.c gray_setup)
+      if (act && P.n_gnodes > 0 && !shadow_hit) {   // conservative fp32 box ray (oracle/rt_oracle.c gray_setup)
         bool miss = false;
+        // (the root box read through an offset opaque to the compiler: it would otherwise load the
+        // twelve words once before the pass loop and hold them in SGPRs across every traversal)
+        int pz = 0;
+        asm volatile("" : "+s"(pz));
+        const double* const root_lo = P.root_lo + pz;
+        const double* const root_hi = P.root_hi + pz;
         const double o3[3] = {ro.x, ro.y, ro.z}, d3v[3] = {rd.x, rd.y, rd.z};
         bool inside = true;
 #pragma unroll
         for (int k = 0; k < 3; ++k)
-          if (!(o3[k] >= P.root_lo[k] && o3[k] <= P.root_hi[k])) inside = false;
+          if (!(o3[k] >= root_lo[k] && o3[k] <= root_hi[k])) inside = false;
         if (!inside) {
           double tn = -DBL_MAX, tf = DBL_MAX;
 #pragma unroll
           for (int k = 0; k < 3; ++k) {
             if (d3v[k] == 0.0) {
-              if (o3[k] < P.root_lo[k] || o3[k] > P.root_hi[k]) miss = true;
+              if (o3[k] < root_lo[k] || o3[k] > root_hi[k]) miss = true;
               continue;
             }
-            double t0 = (P.root_lo[k] - o3[k]) / d3v[k];
-            double t1 = (P.root_hi[k] - o3[k]) / d3v[k];
+            double t0 = (root_lo[k] - o3[k]) / d3v[k];
+            double t1 = (root_hi[k] - o3[k]) / d3v[k];
             if (t0 > t1) { const double t = t0; t0 = t1; t1 = t; }
             if (t0 > tn) tn = t0;
             if (t1 < tf) tf = t1;
@@ -1485,6 +1525,26 @@ __global__ void __launch_bounds__(kBlock, kWavesPerEU * 256 / kBlock) render_ker
         }
       }
       thit = tlim;
+      // (a lane without a ray in a later pass ends it with shadow_hit false)
+      if (kp == 0) sh0 = wballot(shadow_hit);
+      else if (shadow_hit) atomicOr(&lvis[threadIdx.x], 1u << ((batch_end >> kHelpShift) + kp));   // bit: light - batch start
+      // another pass while an owner has a light of its batch left
+      const bool more = state == ST_SHADOW && light + (batch_end >> kHelpShift) + kp + 1 < (batch_end & kEndMask);
+      if (wballot(more) != 0) {
+        if (kp == 0 && (state == ST_CLOSEST || state == ST_HCLOSEST)) {
+          *R.tlim = thit;
+          stk[0] = (uint32_t)best;
+        }
+        continue;
+      }
+      if (kp > 0) {   // later passes ran: every lane's pass-0 result again
+        shadow_hit = lane_bit(sh0);
+        if (state == ST_CLOSEST || state == ST_HCLOSEST) {
+          thit = *R.tlim;
+          best = (int)stk[0];
+        }
+      }
+      break;
     }
     asm volatile("" ::: "memory");
     if (STATS) { const unsigned long long t = stamp(); d_trav += t - t_stamp; t_stamp = t; }
@@ -1504,9 +1564,9 @@ __global__ void __launch_bounds__(kBlock, kWavesPerEU * 256 / kBlock) render_ker
         const unsigned long long x = __shfl_xor(gmax, o);
         gmax = x > gmax ? x : gmax;
       }
-      const unsigned nb = (unsigned)__popcll(wballot(busy));
+      const unsigned nb = (unsigned)__popcll(wballot(state == ST_CLOSEST || state == ST_SHADOW || state >= ST_HSHADOW));
       const unsigned no = (unsigned)__popcll(wballot(state == ST_CLOSEST || state == ST_SHADOW));
-      const unsigned nsh = (unsigned)__popcll(wballot(busy && (state == ST_SHADOW || state == ST_HSHADOW)));
+      const unsigned nsh = (unsigned)__popcll(wballot(state == ST_SHADOW || state == ST_HSHADOW));
       if (lane == 0 && tl_n < (unsigned)kTlCap) {
         unsigned long long* r =
             P.tl + kTlWords * ((size_t)(blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6)) * kTlCap + tl_n);
@@ -1559,7 +1619,7 @@ __global__ void __launch_bounds__(kBlock, kWavesPerEU * 256 / kBlock) render_ker
               (uint32_t)state | (shadow_hit ? 8u : 0u) | ((uint32_t)frame << 4) | ((uint32_t)sample << 11) |
                   ((uint32_t)(refl_h + 1) << 23),
               (uint32_t)it, (uint32_t)depth, (uint32_t)light,
-              ((uint32_t)(batch_end - light) & 63u) | ((uint32_t)(it >> 32) << 6),
+              ((uint32_t)((batch_end & kEndMask) - light) & 63u) | ((uint32_t)(it >> 32) << 6),
               (uint32_t)(state == ST_CLOSEST ? best : mesh), pvo, (uint32_t)px | ((uint32_t)lrow << 16)};
 #pragma unroll
           for (int k = 0; k < kMigWords; ++k) stk[k * kBlock] = w[k];
@@ -1668,14 +1728,16 @@ __global__ void __launch_bounds__(kBlock, kWavesPerEU * 256 / kBlock) render_ker
       // (the ray itself is derived at the start of the next traversal from the slot's closest-hit
       // ray and distance)
       auto launch_batch = [&](double mirror_, const GMat& M_) {
-        c_shadow++;
         state = ST_SHADOW;
         // bit 0 (no helper's: theirs are 1..31): this batch's zero-term rays need no trace (TRAVERSE)
         lvis[threadIdx.x] = (uint32_t)M_.flags & (uint32_t)P.zero_term_lights;
-        batch_end = light + 1;
-        refl_h = -1;
-        // extra lights of this batch, then the reflection ray once the batch covers every light
+        // the whole batch is opened here and every ray of it counted: the owner traces the lights
+        // that the lend step finds no helper for
         const int rest = P.n_lights - light - 1;
+        batch_end = light + 1 + min(rest, kBatchExtra);
+        c_shadow += (unsigned)(batch_end - light);
+        refl_h = -1;
+        // lanes wanted: one per extra light of this batch, then the reflection ray once the batch covers every light
         want = min(rest, kBatchExtra) + ((rest <= kBatchExtra && mirror_ > 0.0 && depth < P.max_depth) ? 1 : 0);
       };
       if (state == ST_SHADOW) {   // batch finished: lights [light, batch_end) in order
@@ -1693,14 +1755,15 @@ __global__ void __launch_bounds__(kBlock, kWavesPerEU * 256 / kBlock) render_ker
         D3 lacc = light == 0 ? d3(0.0 + P.amb[0] * M.ka[0], 0.0 + P.amb[1] * M.ka[1], 0.0 + P.amb[2] * M.ka[2])
                              : LDV(R_LACC);
         const uint32_t vw = lvis[threadIdx.x];
-        for (int j = light; j < batch_end; ++j) {
+        const int bend = batch_end & kEndMask;
+        for (int j = light; j < bend; ++j) {
           const bool occluded = (j == light) ? shadow_hit : (((vw >> (j - light)) & 1u) != 0u);
           // an occluded light adds colour * 0 * (finite term) = +-0, which leaves the sum (never -0)
           // unchanged: skip it (the term is finite for any material with finite shininess >= 0)
           if (!occluded) lacc = add(lacc, contrib_of(j, hp, hn, hview, hdiff, M));
         }
-        light = batch_end;
-        if (light < P.n_lights) {
+        light = bend;
+        if (light < P.n_lights) {   // more than 1 + kBatchExtra lights: the sum so far waits in the path state
           STV(R_LACC, lacc);
           launch_batch(mirror, M);
         } else {   // bounce complete (subtrace, mytracer.cpp:546-555)
@@ -1920,7 +1983,6 @@ __global__ void __launch_bounds__(kBlock, kWavesPerEU * 256 / kBlock) render_ker
             uint32_t tw;
             if (t < n_extra_lights) {
               tw = (uint32_t)lane | ((uint32_t)(t + 1) << 6) | ((uint32_t)(light + 1 + t) << 11);
-              c_shadow++;
             } else {   // reflection ray
               tw = (uint32_t)lane | kTaskRefl;
               c_refl++;
@@ -1928,7 +1990,7 @@ __global__ void __launch_bounds__(kBlock, kWavesPerEU * 256 / kBlock) render_ker
             }
             ltask[ht] = tw;
           }
-          batch_end = light + 1 + min(got, n_extra_lights);
+          batch_end |= min(got, n_extra_lights) << kHelpShift;   // the first light no helper took: light + 1 + that
         }
         wave_lds_sync();
         if (idle) {
