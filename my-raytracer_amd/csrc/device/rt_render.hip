@@ -76,6 +76,15 @@ constexpr int kRefill = RT_REFILL;  // refill a wave when this many lanes are id
 #define RT_REFILL_GATE 0
 #endif
 constexpr bool kRefillGate = RT_REFILL_GATE != 0;
+// One batch of loads per record (0 restores the parent's code for A/B builds):
+// RT_LEAF_PIN  the leaf test keeps all five loads of a triangle record ahead of its first branch;
+// RT_MAT_BATCH SHADE fetches a material's fields, and the normal record, in one or two round trips.
+#ifndef RT_LEAF_PIN
+#define RT_LEAF_PIN 1
+#endif
+#ifndef RT_MAT_BATCH
+#define RT_MAT_BATCH 1
+#endif
 constexpr int kCtrWords = 40;       // [8,16) stats (STATS variants), [16,40) diagnostics (31: guard)
 // Traversal stack: the top kShortStack entries live in an LDS ring (slot i & kStackMask),
 // deeper entries spill to a per-lane global array.  Bounds LDS per block independently
@@ -543,6 +552,76 @@ __device__ __forceinline__ TriOps load_tri(const GTri* tris, uint32_t i) {
   return T;
 }
 
+// A material as SHADE sees it.
+//  Mat<true>: in registers.  A branch fetches what it needs as 16-byte groups of the GMat
+//   q0 ka.xy | q1 ka.z kd.x | q2 kd.yz | q3 ks.xy | q4 ks.z shininess |
+//   q5 mirror, shadowable + draw_mode | q6 tex_w + tex_h, .. | q7 flags (low word), ..
+//  (of q6 and q7 only the first 8 bytes) and pins all of them in ONE empty asm right after the
+//  loads: the loads then all stand before it and go out back to back, one round trip, instead of
+//  being sunk one by one into the branches that first use a field.  The integer fields ride in the
+//  groups as bit patterns (no fp operation touches them).
+//  Mat<false>: every field is read from the record where it is used, and the compiler places the
+//  loads (the code before §14).  The sample-group variants use it -- they have no registers to
+//  keep fields across SHADE's other fetches -- and so does every variant of an RT_MAT_BATCH=0 build.
+typedef double Q2 __attribute__((ext_vector_type(2)));   // one b128 load, one register quad
+template <bool REG>
+struct Mat;
+template <>
+struct Mat<false> {
+  const GMat* g;
+  __device__ __forceinline__ void fetch_head(const GMat* p) { g = p; }
+  __device__ __forceinline__ void fetch_rest(const GMat*) {}
+  __device__ __forceinline__ void fetch_all(const GMat* p) { g = p; }
+  __device__ __forceinline__ D3 ka() const { return d3(g->ka[0], g->ka[1], g->ka[2]); }
+  __device__ __forceinline__ D3 kd() const { return d3(g->kd[0], g->kd[1], g->kd[2]); }
+  __device__ __forceinline__ D3 ks() const { return d3(g->ks[0], g->ks[1], g->ks[2]); }
+  __device__ __forceinline__ double shininess() const { return g->shininess; }
+  __device__ __forceinline__ double mirror() const { return g->mirror; }
+  __device__ __forceinline__ int shadowable() const { return g->shadowable; }
+  __device__ __forceinline__ int draw_mode() const { return g->draw_mode; }
+  __device__ __forceinline__ int tex_w() const { return g->tex_w; }
+  __device__ __forceinline__ int tex_h() const { return g->tex_h; }
+  __device__ __forceinline__ uint32_t flags() const { return (uint32_t)g->flags; }
+};
+template <>
+struct Mat<true> {
+  Q2 q0, q1, q2, q3, q4, q5;
+  double q6, q7;
+  // the fields that decide what SHADE fetches and does next
+  __device__ __forceinline__ void fetch_head(const GMat* p) {
+    const Q2* mq = reinterpret_cast<const Q2*>(p);
+    const double* md = reinterpret_cast<const double*>(p);
+    q5 = mq[5]; q6 = md[12]; q7 = md[14];
+    asm volatile("" : "+v"(q5), "+v"(q6), "+v"(q7));
+  }
+  // ka, kd, ks, shininess
+  __device__ __forceinline__ void fetch_rest(const GMat* p) {
+    const Q2* mq = reinterpret_cast<const Q2*>(p);
+    q0 = mq[0]; q1 = mq[1]; q2 = mq[2]; q3 = mq[3]; q4 = mq[4];
+    asm volatile("" : "+v"(q0), "+v"(q1), "+v"(q2), "+v"(q3), "+v"(q4));
+  }
+  __device__ __forceinline__ void fetch_all(const GMat* p) {
+    const Q2* mq = reinterpret_cast<const Q2*>(p);
+    const double* md = reinterpret_cast<const double*>(p);
+    q0 = mq[0]; q1 = mq[1]; q2 = mq[2]; q3 = mq[3]; q4 = mq[4]; q5 = mq[5]; q6 = md[12]; q7 = md[14];
+    asm volatile("" : "+v"(q0), "+v"(q1), "+v"(q2), "+v"(q3), "+v"(q4), "+v"(q5), "+v"(q6), "+v"(q7));
+  }
+  __device__ __forceinline__ D3 ka() const { return d3(q0.x, q0.y, q1.x); }
+  __device__ __forceinline__ D3 kd() const { return d3(q1.y, q2.x, q2.y); }
+  __device__ __forceinline__ D3 ks() const { return d3(q3.x, q3.y, q4.x); }
+  __device__ __forceinline__ double shininess() const { return q4.y; }
+  __device__ __forceinline__ double mirror() const { return q5.x; }
+  __device__ __forceinline__ int shadowable() const { return __double2loint(q5.y); }
+  __device__ __forceinline__ int draw_mode() const { return __double2hiint(q5.y); }
+  __device__ __forceinline__ int tex_w() const { return __double2loint(q6); }
+  __device__ __forceinline__ int tex_h() const { return __double2hiint(q6); }
+  __device__ __forceinline__ uint32_t flags() const { return (uint32_t)__double2loint(q7); }
+};
+static_assert(offsetof(GMat, kd) == 24 && offsetof(GMat, ks) == 48 && offsetof(GMat, shininess) == 72 &&
+              offsetof(GMat, mirror) == 80 && offsetof(GMat, shadowable) == 88 && offsetof(GMat, draw_mode) == 92 &&
+              offsetof(GMat, tex_w) == 96 && offsetof(GMat, tex_h) == 100 && offsetof(GMat, flags) == 112,
+              "Mat<true> unpacks GMat by its 16-byte groups");
+
 // Work tiles: one wave's 64 pixels, kTileW x kTileH, 8 x 8 (the most coherent primary rays); the
 // unit is also the grain of the cost order (rt_debug_tile_cost and friends).  A tile row of fp32
 // RGB is a 96-B segment, which straddles the image's 64-B HBM write units: the office's 24.9 MB
@@ -671,6 +750,7 @@ template <int WIDTH, bool STATS, bool TL = false, int RING = kShortStack, bool G
 __global__ void __launch_bounds__(kBlock, kWavesPerEU * 256 / kBlock) render_kernel(KParams P) {
   static_assert(RING >= kMigWords && (RING & (RING - 1)) == 0, "ring: a power of two holding the migration words");
   constexpr int kRingMask = RING - 1;
+  constexpr bool kPinMat = RT_MAT_BATCH != 0 && !GRP;   // SHADE keeps materials in registers (Mat<true>)
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
   // LDS: [stack ring: RING rows of kBlock words][slots: kSlotDoubles x kBlock doubles][task words]
   // [visibility words][treelet][lights][pool] -- the ring at address 0 (below)
@@ -1287,8 +1367,15 @@ __global__ void __launch_bounds__(kBlock, kWavesPerEU * 256 / kBlock) render_ker
             // the CPU (bit-identical operands and operation order).  Division-free early
             // rejections first: they fire only where the CPU's rounded quotients certainly
             // fail the same test (margins in DESIGN.md §4), so accept decisions are unchanged.
-            const D3 c4 = sub(ro, T.p2);
+            D3 c4 = sub(ro, T.p2);
             const double S = det3(T.e1, T.e2, c3);
+#if RT_LEAF_PIN
+            // c4 is first used inside the branch below, and the compiler sinks the loads that feed
+            // only it (p2.y, p2.z) into that branch: a second, dependent round trip per triangle
+            // test.  Pinning c4 here keeps the whole record in the one batch of loads issued by
+            // load_tri (same values, same operations: DESIGN.md §14).
+            asm volatile("" : "+v"(c4.x), "+v"(c4.y), "+v"(c4.z));
+#endif
             if (fabs(S) >= 1e-10) {
               const double Da = det3(c4, T.e2, c3);
               const double Db = det3(T.e1, c4, c3);
@@ -1709,7 +1796,8 @@ __global__ void __launch_bounds__(kBlock, kWavesPerEU * 256 / kBlock) render_ker
       D3 scol = d3(0, 0, 0);   // the sample's colour so far once the path ends (finish)
       double mirror = 0.0;
       // lighting() for one light (mytracer.cpp:579-606): Lambert + Phong term of light j
-      auto contrib_of = [&](int j, D3 hp_, D3 hn_, D3 hv_, D3 hd_, const GMat& M) {
+      using MatT = Mat<kPinMat>;
+      auto contrib_of = [&](int j, D3 hp_, D3 hn_, D3 hv_, D3 hd_, const MatT& M) {
         const Light6 L6 = light_of(j);
         const D3 l = nrm(sub(L6.pos, hp_));   // exact: it decides diff > 0 (a discontinuity)
         const double diff = stdmax(0.0, dot(hn_, l));
@@ -1720,17 +1808,18 @@ __global__ void __launch_bounds__(kBlock, kWavesPerEU * 256 / kBlock) render_ker
           refl = stdmax(0.0, dot(r, hv_));
         }
         // pow(+0, y > 0) = +0 exactly: skip the fp64 pow for the (frequent) zero highlight
-        if (!(refl == 0.0 && M.shininess > 0.0)) refl = pow_shade(refl, M.shininess);
-        return d3(L6.col.x * (hd_.x * diff + M.ks[0] * refl), L6.col.y * (hd_.y * diff + M.ks[1] * refl),
-                  L6.col.z * (hd_.z * diff + M.ks[2] * refl));
+        if (!(refl == 0.0 && M.shininess() > 0.0)) refl = pow_shade(refl, M.shininess());
+        const D3 ks = M.ks();
+        return d3(L6.col.x * (hd_.x * diff + ks.x * refl), L6.col.y * (hd_.y * diff + ks.y * refl),
+                  L6.col.z * (hd_.z * diff + ks.z * refl));
       };
       // own shadow ray for light `light`; the rest of the bounce is offered to idle lanes
       // (the ray itself is derived at the start of the next traversal from the slot's closest-hit
       // ray and distance)
-      auto launch_batch = [&](double mirror_, const GMat& M_) {
+      auto launch_batch = [&](double mirror_, const MatT& M_) {
         state = ST_SHADOW;
         // bit 0 (no helper's: theirs are 1..31): this batch's zero-term rays need no trace (TRAVERSE)
-        lvis[threadIdx.x] = (uint32_t)M_.flags & (uint32_t)P.zero_term_lights;
+        lvis[threadIdx.x] = M_.flags() & (uint32_t)P.zero_term_lights;
         // the whole batch is opened here and every ray of it counted: the owner traces the lights
         // that the lend step finds no helper for
         const int rest = P.n_lights - light - 1;
@@ -1748,12 +1837,18 @@ __global__ void __launch_bounds__(kBlock, kWavesPerEU * 256 / kBlock) render_ker
           hview = d3(-rd.x, -rd.y, -rd.z);
         }
         hn = LD_HN();
-        const GMat& M = P.mats[mesh];
-        const D3 hdiff = M.tex_w > 0 ? LDV(R_HD) : d3(M.kd[0], M.kd[1], M.kd[2]);
-        mirror = M.mirror;
+        MatT M;
+        M.fetch_all(P.mats + mesh);   // this branch and contrib_of use every field: one batch of loads
+        const D3 hdiff = M.tex_w() > 0 ? LDV(R_HD) : M.kd();
+        mirror = M.mirror();
         // first batch: the ambient term (mytracer.cpp:574-576) again, else the stored sum
-        D3 lacc = light == 0 ? d3(0.0 + P.amb[0] * M.ka[0], 0.0 + P.amb[1] * M.ka[1], 0.0 + P.amb[2] * M.ka[2])
-                             : LDV(R_LACC);
+        D3 lacc;
+        if (light == 0) {
+          const D3 ka = M.ka();
+          lacc = d3(0.0 + P.amb[0] * ka.x, 0.0 + P.amb[1] * ka.y, 0.0 + P.amb[2] * ka.z);
+        } else {
+          lacc = LDV(R_LACC);
+        }
         const uint32_t vw = lvis[threadIdx.x];
         const int bend = batch_end & kEndMask;
         for (int j = light; j < bend; ++j) {
@@ -1816,14 +1911,22 @@ __global__ void __launch_bounds__(kBlock, kWavesPerEU * 256 / kBlock) render_ker
           hp = add(ro, scl(thit, rd));
           hview = c3;
           D3 hdiff;
+          // In registers (kPinMat): first the fields SHADE decides on.  A shadowable hit needs no more
+          // of the material here (the finished batch reads ka, kd and ks itself); an unshadowed one
+          // fetches the rest below.
+          MatT M;
+          auto ambient = [&]() {   // ambient term (mytracer.cpp:574-576)
+            const D3 ka = M.ka();
+            return d3(0.0 + P.amb[0] * ka.x, 0.0 + P.amb[1] * ka.y, 0.0 + P.amb[2] * ka.z);
+          };
           if (best & kPrimHit) {   // analytic hit (oracle/rt_oracle.c intersect_scene): no texture
             const GPrim& G = P.prims[best & (kPrimHit - 1)];
+            mesh = G.mat;
+            M.fetch_head(P.mats + mesh);   // the material's index comes with the primitive
             hn = G.type == kPrimPlane ? d3(G.n[0], G.n[1], G.n[2])
                                       : d3((ro.x + thit * rd.x - G.c[0]) / G.r, (ro.y + thit * rd.y - G.c[1]) / G.r,
                                            (ro.z + thit * rd.z - G.c[2]) / G.r);
-            mesh = G.mat;
-            const GMat& Mp = P.mats[mesh];
-            hdiff = d3(Mp.kd[0], Mp.kd[1], Mp.kd[2]);
+            if constexpr (!kPinMat) hdiff = M.kd();
           } else {
             // barycentrics and mesh from the leaf test that accepted the hit (slot aux words: the
             // CPU's Da / S and Db / S of mymesh.cpp:205-215 on the same operands); the normal
@@ -1831,44 +1934,54 @@ __global__ void __launch_bounds__(kBlock, kWavesPerEU * 256 / kBlock) render_ker
             const double alpha = *R.a[0], beta = *R.a[1];
             const double gamma = (1.0 - alpha - beta);
             mesh = (int)__double_as_longlong(*R.a[2]);
-            const GMat& Mt = P.mats[mesh];
+            // two round trips: the fields that decide what is fetched next, then the
+            // part of the normal record that the draw mode needs
+            M.fetch_head(P.mats + mesh);
+            const MatT& Mt = M;
             const double* nr = P.tnorm + 12 * (size_t)best;
-            if (Mt.draw_mode == RT_DRAW_FLAT) {   // normals_[i] (mytracer_gpu.cu:498-500)
-              const double2 q0 = *reinterpret_cast<const double2*>(nr);
-              hn = d3(q0.x, q0.y, nr[2]);
+            if (Mt.draw_mode() == RT_DRAW_FLAT) {   // normals_[i] (mytracer_gpu.cu:498-500)
+              Q2 q0 = *reinterpret_cast<const Q2*>(nr);
+              double nz = nr[2];
+              if constexpr (kPinMat) asm volatile("" : "+v"(q0), "+v"(nz));
+              hn = d3(q0.x, q0.y, nz);
             } else {   // alpha*vn0 + beta*vn1 + gamma*vn2, not renormalised (:501-505)
-              const double2* nq = reinterpret_cast<const double2*>(nr + 2);   // [2, 12): _, vn0, vn1, vn2
-              const double2 q1 = nq[0], q2 = nq[1], q3 = nq[2], q4 = nq[3], q5 = nq[4];
+              const Q2* nq = reinterpret_cast<const Q2*>(nr + 2);   // [2, 12): _, vn0, vn1, vn2
+              Q2 q1 = nq[0], q2 = nq[1], q3 = nq[2], q4 = nq[3], q5 = nq[4];
+              if constexpr (kPinMat) asm volatile("" : "+v"(q1), "+v"(q2), "+v"(q3), "+v"(q4), "+v"(q5));
               const double n0[3] = {q1.y, q2.x, q2.y}, n1[3] = {q3.x, q3.y, q4.x}, n2[3] = {q4.y, q5.x, q5.y};
               hn = d3(alpha * n0[0] + beta * n1[0] + gamma * n2[0], alpha * n0[1] + beta * n1[1] + gamma * n2[1],
                       alpha * n0[2] + beta * n1[2] + gamma * n2[2]);
             }
-            if (Mt.tex_w > 0) {
+            if (Mt.tex_w() > 0) {
               const TriShade sh = P.shade[best];
               double u = alpha * P.tu[sh.t[0]] + beta * P.tu[sh.t[1]] + gamma * P.tu[sh.t[2]];
               double v = alpha * P.tv[sh.t[0]] + beta * P.tv[sh.t[1]] + gamma * P.tv[sh.t[2]];
               u = fmin(fmax(u, 0.0), 1.0);   // NaN -> 0, as mytracer_gpu.cu:532-533
               v = fmin(fmax(v, 0.0), 1.0);
-              const unsigned TW = (unsigned)Mt.tex_w, TH = (unsigned)Mt.tex_h;
+              const unsigned TW = (unsigned)Mt.tex_w(), TH = (unsigned)Mt.tex_h();
               const int tx = (int)round(u * (TW - 1));
               const int ty = (int)round((1.0 - v) * (TH - 1));
-              const unsigned char* t3 = P.texels + 3 * (Mt.tex_off + (long long)ty * TW + tx);
+              const unsigned char* t3 = P.texels + 3 * (P.mats[mesh].tex_off + (long long)ty * TW + tx);
               hdiff = d3((double)t3[0] / 255.0, (double)t3[1] / 255.0, (double)t3[2] / 255.0);
-            } else {
-              hdiff = d3(Mt.kd[0], Mt.kd[1], Mt.kd[2]);
+            } else if constexpr (!kPinMat) {
+              hdiff = Mt.kd();
             }
           }
-          const GMat& M = P.mats[mesh];
-          mirror = M.mirror;
-          // ambient term (mytracer.cpp:574-576)
-          D3 lacc = d3(0.0 + P.amb[0] * M.ka[0], 0.0 + P.amb[1] * M.ka[1], 0.0 + P.amb[2] * M.ka[2]);
+          mirror = M.mirror();
+          D3 lacc;
+          if constexpr (!kPinMat) lacc = ambient();
           light = 0;
-          if (M.shadowable && P.n_lights > 0) {   // shadow rays, mytracer.cpp:589-600
+          if (M.shadowable() && P.n_lights > 0) {   // shadow rays, mytracer.cpp:589-600
             ST_HN(hn);
             *R.tlim = thit;   // the slot keeps the closest-hit ray and its distance
-            if (M.tex_w > 0) STV(R_HD, hdiff);
+            if (M.tex_w() > 0) STV(R_HD, hdiff);
             launch_batch(mirror, M);
           } else {
+            if constexpr (kPinMat) {   // unshadowed: lit right here, with the rest of the material in one batch
+              M.fetch_rest(P.mats + mesh);
+              if (!(M.tex_w() > 0)) hdiff = M.kd();
+              lacc = ambient();
+            }
             for (int j = 0; j < P.n_lights; ++j) lacc = add(lacc, contrib_of(j, hp, hn, hview, hdiff, M));
             D3 s0 = d3(0, 0, 0);
             double w = 1.0;
