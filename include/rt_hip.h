@@ -378,6 +378,61 @@ int rt_render_adaptive_to_host(rt_scene* scene, const rt_render_params* p, int s
  * (allocated on first use, grown as needed, freed by rt_scene_free) and one copy. */
 int rt_render_to_host(rt_scene* scene, const rt_render_params* p, void* host_out, rt_stats* stats);
 
+/* Batched ray queries on the device scene: the caller's own rays through the
+ * render path's hierarchy and fp64 triangle test -- picking, line of sight, range sampling.
+ * The ray is Ray(o, d) of the renderer: d is normalised as its `normalize` does (v / |v| per
+ * component, unchanged if |v| = 0) and t is the distance along the normalised direction.  A hit
+ * counts iff 1e-5 < t < tmax (tmax = +inf: unbounded; t = DBL_MAX is never a hit, as on the CPU);
+ * the closest hit is the smallest (t, reference slot), bit-identical to the CPU oracle's
+ * closest_hit.  With rt_scene_set_analytic the spheres and planes are tested first, in the CPU's
+ * order; a triangle must be strictly closer to replace them.  A ray with a non-finite component
+ * in o or d, a zero-length d, a NaN tmax or tmax <= 1e-5 is a miss (not occluded) and is never
+ * traversed. */
+typedef struct rt_ray {
+  double o[3];
+  double d[3];
+  double tmax;
+  double reserved_;
+} rt_ray;   /* 64 B */
+
+/* Triangle hit: slot = the triangle's reference leaf slot (its index in the per-triangle arrays
+ * of the uploaded rt_scene_soa: vertex_idx[3*slot..]), mesh = its mesh id, alpha / beta = the CPU's
+ * Da/S and Db/S, normal = the face normal (RT_DRAW_FLAT) or alpha*vn0 + beta*vn1 + gamma*vn2,
+ * gamma = 1 - alpha - beta, not renormalised (RT_DRAW_PHONG); prim = -1.
+ * Analytic hit: slot = mesh = -1, prim = index (spheres, then planes), alpha = beta = 0, normal =
+ * (p - c) / r or the plane normal.  Miss: t = +inf, slot = mesh = prim = -1, the rest 0. */
+typedef struct rt_hit {
+  double t;
+  double alpha;
+  double beta;
+  double normal[3];
+  int slot;
+  int mesh;
+  int prim;
+  int reserved_;
+} rt_hit;   /* 64 B */
+
+/* Counters of one query: rays traced, rays that hit (closest) or were occluded, traversal-stack
+ * entries spilled from the LDS ring to global memory, waves that tripped the kernel watchdog. */
+typedef struct rt_query_stats {
+  long long rays, hits, stack_spills, watchdog, reserved_[4];
+} rt_query_stats;
+
+/* d_hits[i] = the closest hit of d_rays[i], i in [0, n) (device buffers), on `stream`.
+ * Asynchronous unless stats != NULL, in which case it synchronises the stream and fills *stats
+ * (as rt_launch_compute_image).  n == 0 returns RT_OK without a launch.  Queries take no render
+ * launch context: they may be in flight beside renders and beside each other on different streams
+ * (a ring of 4 query contexts, allocated by the scene's first query).  RT_ERR_HIP on a scene whose
+ * watchdog word is set (rt_scene_status). */
+int rt_trace_closest(rt_scene* scene, const rt_ray* d_rays, long long n, rt_hit* d_hits, rt_query_stats* stats,
+                     void* stream);
+
+/* d_occluded[i] = 1 iff d_rays[i] has some hit with 1e-5 < t < tmax, else 0: an any-hit query
+ * that stops at the first such hit (= "the closest hit has t < tmax").  An analytic primitive
+ * that blocks the ray skips the hierarchy.  Otherwise as rt_trace_closest. */
+int rt_trace_occluded(rt_scene* scene, const rt_ray* d_rays, long long n, unsigned char* d_occluded,
+                      rt_query_stats* stats, void* stream);
+
 /* Cross-process access to a device buffer, for one process per GPU (the frame-assembly mode
  * RT_FLAG_GLOBAL_ROWS: every rank writes its stripes straight into rank 0's frame buffer).
  * rt_ipc_get_handle exports the device allocation that holds d_ptr (an RT_IPC_HANDLE_BYTES-byte

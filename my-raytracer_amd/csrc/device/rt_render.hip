@@ -2436,6 +2436,8 @@ struct LaunchCtx {
   bool used = false;
 };
 
+struct QueryRing;   // ray-query contexts (rt_query.inc)
+
 struct rt_scene {
   int device = 0;
   GNode* d_nodes = nullptr;
@@ -2510,6 +2512,7 @@ struct rt_scene {
   hipStream_t masked[kMaskedStreams] = {};
   hipStream_t masked_for[kMaskedStreams] = {};
   int n_masked = 0;
+  QueryRing* query = nullptr;   // allocated by the scene's first ray query (rt_trace_closest / rt_trace_occluded)
 };
 
 namespace {
@@ -3211,6 +3214,9 @@ struct StreamScratch {
 
 }  // namespace
 
+// batched ray queries on the device scene: kernels, query contexts, rt_trace_closest / rt_trace_occluded
+#include "rt_query.inc"
+
 extern "C" {
 
 int rt_launch_compute_image(rt_scene* sc, const rt_render_params* p, void* d_out, rt_stats* stats, void* stream) {
@@ -3734,6 +3740,7 @@ void rt_scene_free(rt_scene* sc) {
   for (void* q : ptrs)
     if (q) (void)hipFree(q);
   if (sc->h_guard) (void)hipHostFree(sc->h_guard);
+  query_ring_free(sc);
   for (LaunchCtx& c : sc->ctx) {
     void* cp[] = {c.d_ctr, c.d_pstate, c.d_spill, c.d_wavelog, c.d_tl, c.d_wctr};
     for (void* q : cp)

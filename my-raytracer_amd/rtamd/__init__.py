@@ -391,6 +391,50 @@ class DeviceScene:
                                                C.byref(st)), "rt_render_to_host")
         return img, st
 
+    def trace(self, rays, occluded=False, stats=False, stream=None):
+        """Batched ray query (rt_trace_closest / rt_trace_occluded).  rays: [n, 8] float64 rows
+        (o xyz, d xyz, tmax, reserved) -- a CUDA tensor on the scene's device, used in place, or a
+        numpy array, uploaded.  Closest hits come back as a dict of views of one [n, 8] float64
+        result buffer (rt_hit rows): t, alpha, beta, normal [n, 3], and slot, mesh, prim as int32;
+        occluded=True returns a uint8 array instead.  Tensors in, tensors out (asynchronous on
+        `stream`, an int pointer, None = the null stream, unless stats=True); numpy in, numpy out.
+        stats=True returns (result, QueryStats)."""
+        import torch
+
+        host_in = isinstance(rays, np.ndarray)
+        dev = torch.device(f"cuda:{self.device}")
+        if host_in:
+            if rays.ndim != 2 or rays.shape[1] != 8:
+                raise ValueError("rays must be an [n, 8] float64 array")
+            rays = torch.from_numpy(np.ascontiguousarray(rays, dtype=np.float64)).to(dev)
+        if not (isinstance(rays, torch.Tensor) and rays.dtype == torch.float64 and rays.dim() == 2
+                and rays.shape[1] == 8 and rays.is_contiguous() and rays.device == dev):
+            raise ValueError(f"rays must be a contiguous [n, 8] float64 tensor on {dev}")
+        n = rays.shape[0]
+        st = abi.QueryStats() if stats else None
+        if occluded:
+            out = torch.zeros((n,), dtype=torch.uint8, device=dev)
+            fn, what = hip_lib().rt_trace_occluded, "rt_trace_occluded"
+        else:
+            out = torch.zeros((n, 8), dtype=torch.float64, device=dev)
+            fn, what = hip_lib().rt_trace_closest, "rt_trace_closest"
+        if stream:   # the buffers above were made on torch's current stream
+            torch.cuda.current_stream(dev).synchronize()
+        _check_hip(fn(self._h, C.c_void_p(rays.data_ptr() if n else None), n, C.c_void_p(out.data_ptr() if n else None),
+                      C.byref(st) if st is not None else None, C.c_void_p(stream) if stream else None), what)
+        if host_in:
+            torch.cuda.synchronize(dev)
+            out = out.cpu()
+        if occluded:
+            res = out.numpy() if host_in else out
+        else:
+            ints = out.view(torch.int32)
+            res = {"t": out[:, 0], "alpha": out[:, 1], "beta": out[:, 2], "normal": out[:, 3:6],
+                   "slot": ints[:, 12], "mesh": ints[:, 13], "prim": ints[:, 14]}
+            if host_in:
+                res = {k: v.numpy() for k, v in res.items()}
+        return (res, st) if stats else res
+
     def debug_counters(self):
         """Raw counter words of the last launch (see rt_debug_counters in rt_hip.h)."""
         buf = (C.c_ulonglong * 40)()
@@ -490,6 +534,25 @@ def shard_rows(height, stripe_height, stripe_count, stripe_index):
     """Global row ids a shard renders, in output order (rt_render_params rules)."""
     y = np.arange(height)
     return y[(y // stripe_height) % stripe_count == stripe_index]
+
+
+def camera_rays(params):
+    """The primary rays of params.camera as [H * W, 8] float64 rows for DeviceScene.trace
+    (o = eye, d, tmax = inf, reserved 0), row-major with row 0 at the bottom (pixel (x, y) at row
+    y * W + x).  The direction is evaluated in the renderer's order,
+    ((lower_left + x * x_dir) + y * y_dir) - eye, and left unnormalised (the query normalises)."""
+    cam = params.camera
+    W, H = cam.width, cam.height
+    eye, ll = np.array(cam.eye[:]), np.array(cam.lower_left[:])
+    xd, yd = np.array(cam.x_dir[:]), np.array(cam.y_dir[:])
+    x = np.arange(W, dtype=np.float64)[None, :, None]
+    y = np.arange(H, dtype=np.float64)[:, None, None]
+    d = ((ll + x * xd) + y * yd) - eye
+    rays = np.zeros((H * W, 8))
+    rays[:, 0:3] = eye
+    rays[:, 3:6] = d.reshape(-1, 3)
+    rays[:, 6] = np.inf
+    return rays
 
 
 def camera_orbit(params, angle):

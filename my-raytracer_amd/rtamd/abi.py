@@ -137,6 +137,25 @@ class Stats(C.Structure):
         return {name: int(getattr(self, name)) for name, _ in self._fields_ if name != "reserved_"}
 
 
+class Ray(C.Structure):
+    """rt_ray: one row of a [n, 8] float64 ray array (o, d, tmax, reserved)."""
+    _fields_ = [("o", c_double3), ("d", c_double3), ("tmax", C.c_double), ("reserved_", C.c_double)]
+
+
+class Hit(C.Structure):
+    """rt_hit: one row of a [n, 8] float64 result array (the four ints share its last two words)."""
+    _fields_ = [("t", C.c_double), ("alpha", C.c_double), ("beta", C.c_double), ("normal", c_double3),
+                ("slot", C.c_int), ("mesh", C.c_int), ("prim", C.c_int), ("reserved_", C.c_int)]
+
+
+class QueryStats(C.Structure):
+    _fields_ = [("rays", C.c_longlong), ("hits", C.c_longlong), ("stack_spills", C.c_longlong),
+                ("watchdog", C.c_longlong), ("reserved_", C.c_longlong * 4)]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_ if name != "reserved_"}
+
+
 class GenParams(C.Structure):
     _fields_ = [("width", C.c_int), ("height", C.c_int), ("n_triangles", C.c_longlong),
                 ("seed", C.c_ulonglong), ("max_depth", C.c_int), ("detail", C.c_int)]
@@ -184,6 +203,10 @@ HIP_SYMBOLS = {
     "rt_render_to_host": (C.c_int, [C.c_void_p, C.POINTER(RenderParams), C.c_void_p, C.POINTER(Stats)]),
     "rt_render_adaptive_to_host": (C.c_int, [C.c_void_p, C.POINTER(RenderParams), C.c_int, C.c_double, C.c_void_p,
                                              C.POINTER(Stats), C.POINTER(Stats), C.POINTER(C.c_longlong)]),
+    "rt_trace_closest": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.POINTER(QueryStats),
+                                   C.c_void_p]),
+    "rt_trace_occluded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.POINTER(QueryStats),
+                                    C.c_void_p]),
     "rt_last_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "rt_tile_shape": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "rt_ipc_get_handle": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_ulonglong)]),
