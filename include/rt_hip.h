@@ -476,8 +476,11 @@ int rt_scene_status(const rt_scene* scene);
  * in word 9) whose light faces away from a surface of a material with shininess
  * > 0 and finite coefficients, all light colours finite, so that their light term
  * is exactly 0 -- not traced by the production kernels; with a STATS or timeline
- * flag they are traced and only counted.
- * Returns the number of words copied (at most 40). */
+ * flag they are traced and only counted; word 39 = internal; words 40, 41 (4-wide STATS flag) =
+ * wave-level node iterations in which some active lane's stack ring had fewer than three free
+ * entries (the pushes take the path that can spill), and those that popped while some active
+ * lane had entries in the spill array.
+ * Returns the number of words copied (at most 42). */
 int rt_debug_counters(rt_scene* scene, unsigned long long* out, int n);
 
 /* Diagnostics: per-wave timeline of the last launch with a STATS flag: words

@@ -85,7 +85,27 @@ constexpr bool kRefillGate = RT_REFILL_GATE != 0;
 #ifndef RT_MAT_BATCH
 #define RT_MAT_BATCH 1
 #endif
-constexpr int kCtrWords = 40;       // [8,16) stats (STATS variants), [16,40) diagnostics (31: guard)
+// Stack traffic and child counting of the 4-wide node loop, one bit per step; 0 is
+// the parent's algorithm, for A/B builds (not its text: the sort is written under the test for a hit
+// child, where the parent's compiler had sunk it; within noise of the parent commit's library).  Visit order and push order are the parent's in every step.
+//    1  sorted path: one wave-uniform capacity test per iteration, then unconditional ring writes;
+//    2  the same for waves of any-hit rays;
+//    4  a pop without branches while no active lane has spilled entries;
+//    8  a lane with one hit child takes it without the sort (a wave whose lanes all hit at most
+//       one child skips the sorting network);
+//   32  the tests on the number of hit children (0, > 1, > 2, > 3) are scalar logic on the four
+//       compare masks instead of a per-lane count and compares.
+// On: 1, 8, 32.  Steps 2 and 4 measured slower than the parent on the office, step 1 too without
+// step 32 (§16.3); they stay here switched off.  (Bit 16, pushes that keep their branches under the
+// capacity test, measured -0.6 % and was removed.)
+#ifndef RT_STACK_FAST
+#define RT_STACK_FAST 41
+#endif
+constexpr bool kFastSort = (RT_STACK_FAST & 1) != 0, kFastAny = (RT_STACK_FAST & 2) != 0, kFastPop = (RT_STACK_FAST & 4) != 0;
+constexpr bool kOneHit = (RT_STACK_FAST & 8) != 0, kMaskCnt = (RT_STACK_FAST & 32) != 0;
+static_assert((RT_STACK_FAST & ~47) == 0, "RT_STACK_FAST: bits 1, 2, 4, 8 and 32");
+constexpr bool kRoomTest = kFastSort || kFastAny;
+constexpr int kCtrWords = 42;       // [8,16) stats (STATS variants), [16,42) diagnostics (31: guard)
 // Traversal stack: the top kShortStack entries live in an LDS ring (slot i & kStackMask),
 // deeper entries spill to a per-lane global array.  Bounds LDS per block independently
 // of tree depth, so occupancy stays VGPR-limited.
@@ -209,8 +229,10 @@ enum : int {
   CD_LEAF_LINES, CD_BIG_LEAF_TESTS, CD_NODE_LDS_ITERS, CD_GUARD = 31,   // CD_GUARD: a wave hit the iteration guard
   CD_GNODE_UNIFORM = 32, CD_GNODE_DISTINCT, CD_LEAF_UNIFORM, CD_ANYHIT_TRIS, CD_OWN_TRIS,
   CD_ZERO_TERM,   // shadow rays whose light term is exactly 0: not traced (diagnostic variants: traced, counted)
-  CT_ORDER_JOBS = 39   // cost-ordered launches: order / zeroing jobs claimed by blocks that finished
+  CT_ORDER_JOBS = 39,  // cost-ordered launches: order / zeroing jobs claimed by blocks that finished
+  CD_SLOW_PUSH = 40, CD_SLOW_POP   // 4-wide node iterations that took the slow push / slow pop path (RT_STACK_FAST)
 };
+static_assert(kCtrWords * sizeof(unsigned long long) <= 512, "the counter words end where the work heads begin");
 // Watchdogs (never reached by a correct kernel): the persistent loop, and the wave-level
 // iterations of one traversal round (round, node and leaf loops together).  A wave that
 // trips either ends its work instead of spinning and flags the launch (CD_GUARD), which
@@ -887,6 +909,7 @@ __global__ void __launch_bounds__(kBlock, kWavesPerEU * 256 / kBlock) render_ker
   unsigned long long d_node_it = 0, d_node_ln = 0, d_leaf_it = 0, d_leaf_ln = 0;
   unsigned long long d_trav = 0, d_shade = 0, d_fetch = 0, d_outer = 0, d_round_it = 0, d_round_ln = 0;
   unsigned long long d_spills = 0, d_node_lines = 0, d_leaf_lines = 0, d_big_leaf = 0, d_node_lds = 0, d_dummy = 0, d_gn_uni = 0, d_gn_dist = 0, d_leaf_uni = 0;
+  unsigned long long d_slow_push = 0, d_slow_pop = 0;
   unsigned long long d_any_tris = 0, d_own_tris = 0;   // any-hit triangle tests; of those, the ray's own record
   unsigned long long w_start = STATS ? __builtin_amdgcn_s_memrealtime() : 0ull, w_refill = 0, w_pixels = 0;
   unsigned long long t_stamp = 0;
@@ -1322,6 +1345,14 @@ __global__ void __launch_bounds__(kBlock, kWavesPerEU * 256 / kBlock) render_ker
         sqlim = sq + kRingB;
         return spill[(size_t)(sq / kSW) * P.nslots];
       };
+      // pop while the lane has no spilled entries (sqlim == kRingB: the ring holds the whole stack):
+      // an unconditional read below the top (of a dead ring slot when the stack is empty) and selects
+      auto pop_fast = [&]() -> uint32_t {
+        const uint32_t x = ring(sq - kSW);
+        const bool empty = sq == 0;
+        sq -= empty ? 0u : kSW;
+        return empty ? kDone : x;
+      };
       const D3 c3 = d3(-rd.x, -rd.y, -rd.z);
 
       // Watchdog of the traversal loops that could cycle on a corrupt hierarchy (the round loop
@@ -1495,6 +1526,7 @@ __global__ void __launch_bounds__(kBlock, kWavesPerEU * 256 / kBlock) render_ker
           float k[4];
           uint32_t v[4];
           bool hb[4];   // child hit (any-hit waves test these; the keys and count then serve only the sort)
+          unsigned long long mh[4] = {0, 0, 0, 0};   // the same as wave masks
           int cnt = 0;
           float4 nx, fx, ny, fy, nz, fz;
           uint4 rf;
@@ -1532,6 +1564,24 @@ __global__ void __launch_bounds__(kBlock, kWavesPerEU * 256 / kBlock) render_ker
             rf = *reinterpret_cast<const uint4*>(RT_NODE_AT(96u));
 #undef RT_NODE_AT
           }
+          // Stack traffic of the iteration.  Two wave-uniform tests stand in for the
+          // per-push and per-pop branches of steps 1, 2 and 4: `room` -- every active lane's ring
+          // takes three more entries without a spill, so the pushes are plain ring writes; `nosp` --
+          // no active lane has spilled entries, so a pop is a ring read.  Where a test fails the wave
+          // runs the general push / pop.  Both test values known when the iteration starts: the
+          // opaque operands and the scheduling barrier keep the two compares ahead of the wait for
+          // the node.  The diagnostic variants evaluate both whatever the switch and count the
+          // iterations that fail them (CD_SLOW_PUSH, CD_SLOW_POP).
+          unsigned long long m_spilled = 0, m_full = 0;
+          if (kFastPop || STATS) m_spilled = wballot(sqlim != kRingB);
+          if (kRoomTest || STATS) m_full = wballot(sq + 3u * kSW > sqlim);
+          if (kRoomTest || kFastPop) {
+            asm volatile("" : "+s"(m_spilled), "+s"(m_full));
+            __builtin_amdgcn_sched_barrier(0);
+          }
+          bool nosp = (kFastPop || STATS) && m_spilled == 0;
+          const bool room = (kRoomTest || STATS) && m_full == 0;
+          bool slow_popped = false;
 #pragma unroll
           for (int c = 0; c < 4; ++c) {
             const float tx0 = __builtin_fmaf(f4c(nx, c), ivx, -oix), tx1 = __builtin_fmaf(f4c(fx, c), ivx, -oix);
@@ -1545,6 +1595,7 @@ __global__ void __launch_bounds__(kBlock, kWavesPerEU * 256 / kBlock) render_ker
             const uint32_t r = u4c(rf, c);
             const bool h = tn <= tf;   // absent children carry the empty box [+inf, -inf]
             hb[c] = h;
+            if (kMaskCnt) mh[c] = wballot(h);   // (taken beside the compare: the compare's own mask)
             k[c] = h ? tn : INFINITY;
             v[c] = r;
             cnt += h ? 1 : 0;
@@ -1554,33 +1605,82 @@ __global__ void __launch_bounds__(kBlock, kWavesPerEU * 256 / kBlock) render_ker
     const float tk = k[a]; k[a] = k[b]; k[b] = tk;            \
     const uint32_t tv = v[a]; v[a] = v[b]; v[b] = tv;         \
   }
+          auto pop_it = [&]() -> uint32_t {
+            if (kFastPop && nosp) return pop_fast();
+            if (STATS && !nosp) slow_popped = true;
+            return pop();
+          };
+          if (STATS && !room) wave_tick(d_slow_push, d_dummy, lane);
           if (w_any) {   // a wave of any-hit rays: the last hit child first, the others pushed
             // (orders chosen per lane or per wave from the ray's entry distances lost 2-11 %, the
             // swaps' cost included; the fixed first-slot-first order 4 %: DESIGN.md §4)
             uint32_t nxt = kDone;
+            if (kFastAny && room) {
+              // children 0..2 are written in slot order at a position that advances only past a hit
+              // one: a missed child's word is overwritten by the next write or stays above the top.
+              // The last hit child is not pushed but visited: child 3 if hit (then all written
+              // entries stay), else the topmost written entry, which is dropped again.
+              uint32_t p = sq;
+#pragma unroll
+              for (int c = 0; c < 3; ++c) {
+                ring(p) = v[c];
+                p += hb[c] ? kSW : 0u;
+                nxt = hb[c] ? v[c] : nxt;
+              }
+              const uint32_t below = p != sq ? p - kSW : p;
+              sq = hb[3] ? p : below;
+              nxt = hb[3] ? v[3] : nxt;
+            } else {
 #pragma unroll
             for (int c = 0; c < 4; ++c)
               if (hb[c]) {
                 if (nxt != kDone) push(nxt);
                 nxt = v[c];
               }
-            cur = nxt == kDone ? pop() : nxt;
+            // (a push only adds spilled entries, and only lanes that were tested pushed)
+            if ((kFastPop || STATS) && !room) nosp = nosp && wballot(sqlim != kRingB) == 0;
+            }
+            cur = nxt == kDone ? pop_it() : nxt;
+          } else {
+          // how many children were hit, as tests on the hit masks (scalar logic) or on the count
+          const unsigned long long m0 = mh[0], m1 = mh[1], m2 = mh[2], m3 = mh[3];
+          const unsigned long long h01 = m0 | m1, h23 = m2 | m3, b01 = m0 & m1, b23 = m2 & m3;
+          const bool ge1 = kMaskCnt ? __builtin_amdgcn_inverse_ballot_w64(h01 | h23) : cnt != 0;
+          const bool ge2 = kMaskCnt ? __builtin_amdgcn_inverse_ballot_w64(b01 | b23 | (h01 & h23)) : cnt > 1;
+          const bool ge3 = kMaskCnt ? __builtin_amdgcn_inverse_ballot_w64((b01 & h23) | (b23 & h01)) : cnt > 2;
+          const bool ge4 = kMaskCnt ? __builtin_amdgcn_inverse_ballot_w64(b01 & b23) : cnt > 3;
+          if (!ge1) {
+            cur = pop_it();
+          } else if (kOneHit && !ge2) {   // nothing to sort, nothing to push: the hit child
+            cur = hb[0] ? v[0] : hb[1] ? v[1] : hb[2] ? v[2] : v[3];
           } else {
           RT_CSWAP(0, 1) RT_CSWAP(2, 3) RT_CSWAP(0, 2) RT_CSWAP(1, 3) RT_CSWAP(1, 2)
-          if (cnt == 0) {
-            cur = pop();
+          if (kFastSort && room) {
+            // far-first at a running position that advances only past a hit child (above)
+            uint32_t p = sq;
+            ring(p) = v[3];
+            p += ge4 ? kSW : 0u;
+            ring(p) = v[2];
+            p += ge3 ? kSW : 0u;
+            ring(p) = v[1];
+            p += ge2 ? kSW : 0u;
+            sq = p;
           } else {
-            if (cnt > 3) push(v[3]);
-            if (cnt > 2) push(v[2]);
-            if (cnt > 1) push(v[1]);
-            cur = v[0];
+            if (ge4) push(v[3]);
+            if (ge3) push(v[2]);
+            if (ge2) push(v[1]);
           }
+          cur = v[0];
+          }
+          // (a push only adds spilled entries)
+          if ((kFastPop || STATS) && !room) nosp = nosp && wballot(sqlim != kRingB) == 0;
           }
 #undef RT_CSWAP
           if ((cur & kLeaf) && cur != kDone && pleaf == kDone) {   // first leaf: postpone, keep going
             pleaf = cur;
-            cur = pop();
+            cur = pop_it();
           }
+          if (STATS && wballot(slow_popped) != 0) wave_tick(d_slow_pop, d_dummy, lane);
           if ((wballot(pleaf == kDone) & wballot(cur != kDone)) == 0) break;   // every lane holds a leaf (one mask per compare)
         }
         }
@@ -2155,7 +2255,10 @@ __global__ void __launch_bounds__(kBlock, kWavesPerEU * 256 / kBlock) render_ker
     const unsigned long long r = wave_sum(d_big_leaf), t = wave_sum(d_node_lds);
     const unsigned long long gu = wave_sum(d_gn_uni), gd = wave_sum(d_gn_dist), lu = wave_sum(d_leaf_uni);
     const unsigned long long at = wave_sum(d_any_tris), ot = wave_sum(d_own_tris);
+    const unsigned long long pu = wave_sum(d_slow_push), po = wave_sum(d_slow_pop);
     if (lane == 0) {
+      atomicAdd(&P.ctr[CD_SLOW_PUSH], pu);
+      atomicAdd(&P.ctr[CD_SLOW_POP], po);
       atomicAdd(&P.ctr[CD_ANYHIT_TRIS], at);
       atomicAdd(&P.ctr[CD_OWN_TRIS], ot);
       atomicAdd(&P.ctr[CD_NODE_LDS_ITERS], t);
