@@ -433,6 +433,40 @@ int rt_trace_closest(rt_scene* scene, const rt_ray* d_rays, long long n, rt_hit*
 int rt_trace_occluded(rt_scene* scene, const rt_ray* d_rays, long long n, unsigned char* d_occluded,
                       rt_query_stats* stats, void* stream);
 
+/* Radiance of the caller's own rays: panoramas, fisheye or thin-lens cameras,
+ * probes, re-shading the hit points of a query, sparse sampling.
+ * d_rgb[3*i .. 3*i+2] = the colour trace() returns for ray i (what a pixel whose one primary ray
+ * is d_rays[i] would hold), i in [0, n), clamped to 1 per channel, in p->out_format (device
+ * buffers, 3 floats or 3 doubles per ray), on `stream`.  The render kernel itself shades them --
+ * lights, shadows, mirrors to p->max_depth, textures, analytic primitives -- with the operations of
+ * a frame launch: the rays of a camera (pixel (x, y): o = eye, d = lower_left + x x_dir + y y_dir -
+ * eye) give that frame's bits.  A wave takes 64 consecutive rays, so the caller's ray order decides
+ * their coherence (8x8 pixel tiles are the render's own order); results do not depend on it.
+ *   The ray is Ray(o, d) as for the queries above: d is normalised by the renderer.  tmax bounds the
+ * primary segment only: the ray hits iff 1e-5 < t < tmax (+inf or DBL_MAX: unbounded), else it
+ * takes the background; shadow and reflection rays keep their own limits.  A degenerate ray
+ * (non-finite component in o or d, zero-length d, NaN tmax or tmax <= 1e-5) is never traversed,
+ * is not counted in primary_rays and gets the background colour.
+ *   Read from p: the lights (inline, or lights_ext at any count up to RT_LIGHTS_LIMIT), max_depth,
+ * background, ambience, out_format.  p->camera is ignored.  RT_ERR_INVALID, before any HIP call,
+ * for: a NULL scene or p; n < 0; n > 0 with a NULL buffer; n > RT_RADIANCE_MAX_RAYS (the ray
+ * index travels in 32 bits of path state, its work unit of 64 rays in 31); spp_n != 1; a row range
+ * or stripes other than the defaults (row_begin = 0, row_end <= 0 or = camera.height, stripe_count
+ * <= 1, stripe_index = 0); an unknown out_format; any flag but RT_FLAG_NATURAL_ORDER, which is accepted and changes
+ * nothing.  n == 0 returns RT_OK without a launch and touches nothing.
+ *   It is a render launch: it takes one of the scene's 8 launch contexts, copies its light table
+ * with its control block, runs beside other launches on other streams under the rules of
+ * rt_launch_compute_image, honours reserve_cus / blocks_per_cu / grid_spare (the persistent grid
+ * is sized from ceil(n / 64) waves), is reported by rt_last_kernel_ms and rt_debug_last_grid, and
+ * returns RT_ERR_HIP on a scene whose watchdog word is set.  It neither reads nor records tile
+ * costs or orders: frame launches after it behave as if it had not happened.
+ *   Asynchronous unless stats != NULL (then it synchronises the stream): primary_rays = the rays
+ * traced (degenerate ones excluded), shadow_rays / reflection_rays as for renders, pixels = n,
+ * the counter-variant fields 0. */
+#define RT_RADIANCE_MAX_RAYS (1LL << 31)
+int rt_trace_radiance(rt_scene* scene, const rt_render_params* p, const rt_ray* d_rays, long long n,
+                      void* d_rgb, rt_stats* stats, void* stream);
+
 /* Cross-process access to a device buffer, for one process per GPU (the frame-assembly mode
  * RT_FLAG_GLOBAL_ROWS: every rank writes its stripes straight into rank 0's frame buffer).
  * rt_ipc_get_handle exports the device allocation that holds d_ptr (an RT_IPC_HANDLE_BYTES-byte
@@ -491,7 +525,8 @@ long long rt_debug_wave_log(rt_scene* scene, unsigned long long* out, long long 
 
 /* Diagnostics: persistent-grid blocks per CU of kernel variant 0 (production), 1 (4-wide
  * STATS), 2 (2-wide canonical STATS), 3 (timeline), 4 (production, 16-entry stack ring), 5 / 6
- * (0 / 4 with sample groups, spp > 1), as the launches use it. */
+ * (0 / 4 with sample groups, spp > 1), 7 / 8 (0 / 4 over a ray list, rt_trace_radiance), as the
+ * launches use it. */
 int rt_debug_blocks_per_cu(rt_scene* scene, int variant);
 
 /* Diagnostics: the persistent grid (blocks) the last launch on the scene used, and the grid a

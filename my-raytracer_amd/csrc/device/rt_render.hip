@@ -36,6 +36,12 @@
 //     mytracer.cpp:547); the reference GPU traces max_depth zero-weight
 //     bounces (mytracer_gpu.cu:281-310) — same pixels, less work.
 // No MFMA: the path is a traversal / latency problem.
+//
+// The kernel is compiled twice from its one text: as render_kernel (frames), and, through this
+// file including itself once below the kernel with RT_RAY_LIST_PASS set, as radiance_kernel
+// (rt_trace_radiance: the work items are a caller's rays).  Everything but the
+// kernel sits in the two #ifndef RT_RAY_LIST_PASS regions before and after it.
+#ifndef RT_RAY_LIST_PASS
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
@@ -354,7 +360,12 @@ struct KParams {
   // tile order (RT_FLAG_COST_ORDER): work item w belongs to linear tile tile_order[w / 64] instead of
   // w / 64 (a permutation within each work head's range); tile_cost[ty * tiles_x + tx] accumulates
   // the cost of the tile position's finished samples over the launch's frames (the next order)
-  const uint32_t* tile_order;
+  // (a ray-list launch, rt_trace_radiance, has no tile order and no drain jobs: its ray buffer and
+  // ray count take the places of tile_order and n_pos, so the block keeps its layout)
+  union {
+    const uint32_t* tile_order;
+    const rt_ray* rays;        // ray list: work item w is rays[w]
+  };
   uint32_t* tile_cost;
   int cost_time;            // tile_cost in 10-ns ticks of pixel lifetime instead of bounces
   DivMagic div_row_tiles, div_tiles_x, div_stripe_h;   // n / (frames x tiles_x), n / tiles_x, n / stripe_h
@@ -363,7 +374,10 @@ struct KParams {
   const uint32_t* order_src;   // complete per-position cost map (an earlier launch's)
   uint32_t* next_order;        // its tile order, for the launch after this one
   uint32_t* zero_map;          // cost map to clear for the launch after this one
-  long long n_pos;             // tile positions (= tiles of a one-frame launch)
+  union {
+    long long n_pos;           // tile positions (= tiles of a one-frame launch)
+    long long n_rays;          // ray list: rays of the launch
+  };
 };
 
 // ---- fp64 vector ops (course vec4 semantics on xyz) ----
@@ -768,8 +782,22 @@ __device__ void order_range(const uint32_t* cost, uint32_t* order, long long n_t
   }
 }
 
+#endif   // !RT_RAY_LIST_PASS
+
+// RAYS (the second pass over this text): work item w is ray w of P.rays, its colour goes to 3 w of the
+// launch's one output buffer -- no tiles, frames, samples or cost maps; the ray index travels in
+// (px, lrow) as its low and high 16 bits (registers, donation word).  Always the production kernel:
+// 4-wide, no counters, no timeline, no sample groups.
+#ifndef RT_RAY_LIST_PASS
 template <int WIDTH, bool STATS, bool TL = false, int RING = kShortStack, bool GRP = false>
 __global__ void __launch_bounds__(kBlock, kWavesPerEU * 256 / kBlock) render_kernel(KParams P) {
+  constexpr bool RAYS = false;
+#else
+template <int RING>
+__global__ void __launch_bounds__(kBlock, kWavesPerEU * 256 / kBlock) radiance_kernel(KParams P) {
+  constexpr int WIDTH = 4;
+  constexpr bool STATS = false, TL = false, GRP = false, RAYS = true;
+#endif
   static_assert(RING >= kMigWords && (RING & (RING - 1)) == 0, "ring: a power of two holding the migration words");
   constexpr int kRingMask = RING - 1;
   constexpr bool kPinMat = RT_MAT_BATCH != 0 && !GRP;   // SHADE keeps materials in registers (Mat<true>)
@@ -883,8 +911,9 @@ __global__ void __launch_bounds__(kBlock, kWavesPerEU * 256 / kBlock) render_ker
 
   // wave-uniform work-head cursor; in list mode the work count comes from the device
   // work items of the list mode: one per (listed pixel, sample), or per listed pixel with sample groups
-  const long long n_list = P.list ? (long long)*P.list_count * (group_log ? 1 : P.nsamp) : 0;
-  const long long n_tiles = P.list ? (n_list + 63) / 64 : P.n_tiles;
+  // (RAYS: ceil(n_rays / 64) "tiles" of 64 consecutive rays, set by the host)
+  const long long n_list = !RAYS && P.list ? (long long)*P.list_count * (group_log ? 1 : P.nsamp) : 0;
+  const long long n_tiles = !RAYS && P.list ? (n_list + 63) / 64 : P.n_tiles;
   int head = blockIdx.x % kGroups;
   int heads_left = kGroups;
 
@@ -1001,6 +1030,28 @@ __global__ void __launch_bounds__(kBlock, kWavesPerEU * 256 / kBlock) render_ker
     emit_ray(d3(K.eye[0], K.eye[1], K.eye[2]), dir, DBL_MAX);
     state = ST_CLOSEST;
   };
+  // RAYS: the primary ray is the caller's 64-B rt_ray instead (o, d, tmax), read with four 16-B loads
+  // issued together through rr, the wave's window of the ray buffer (at most 64 rays, ending at the
+  // buffer's last ray), at byte offset vo.  d is normalised by emit_ray like every ray here, so a camera's
+  // rays give the render's bits; tmax bounds this segment only (a hit counts iff t < tmax).  A degenerate
+  // ray (non-finite o or d, |d| = 0, NaN tmax or tmax <= 1e-5) is not started and not
+  // counted: false, and the caller stores the background for it.
+  [[maybe_unused]] auto start_ray = [&](__amdgpu_buffer_rsrc_t rr, uint32_t vo) -> bool {
+    const D2 q0 = buf_ld2(rr, vo, 0), q1 = buf_ld2(rr, vo + 16u, 0), q2 = buf_ld2(rr, vo + 32u, 0),
+             q3 = buf_ld2(rr, vo + 48u, 0);
+    const D3 ro = d3(q0.a, q0.b, q1.a);
+    const D3 dv = d3(q1.b, q2.a, q2.b);
+    const double tmax = q3.a;
+    auto fin = [](double x) { return fabs(x) <= DBL_MAX; };   // false for NaN / inf
+    const bool ok = fin(ro.x) && fin(ro.y) && fin(ro.z) && fin(dv.x) && fin(dv.y) && fin(dv.z) &&
+                    sqrt(dot(dv, dv)) > 0.0 && tmax > 1e-5;   // NaN tmax: false
+    if (!ok) return false;
+    depth = 0;
+    c_primary++;
+    emit_ray(ro, dv, tmax < DBL_MAX ? tmax : DBL_MAX);
+    state = ST_CLOSEST;
+    return true;
+  };
   // compute_image's last step for the pixel (px, lrow, frame): average the sum over the n x n
   // samples, clamp, store (mytracer_gpu.cu:155-159, 221-227)
   auto store_pixel = [&](D3 pcol) {
@@ -1008,7 +1059,9 @@ __global__ void __launch_bounds__(kBlock, kWavesPerEU * 256 / kBlock) render_ker
     asm volatile("" : "+s"(n2));   // converted here, not hoisted into a VGPR live across the loop
     const double nn = (double)n2;
     double r, g, b;
-    if ((n2 & (n2 - 1)) == 0) {
+    if (RAYS) {   // one sample: no average
+      r = stdmin(pcol.x, 1.0); g = stdmin(pcol.y, 1.0); b = stdmin(pcol.z, 1.0);
+    } else if ((n2 & (n2 - 1)) == 0) {
       // n2 = 2^k: x / n2 = x * 2^-k exactly (one rounding of the same exact value), no division
       const double s = __builtin_ldexp(1.0, -__builtin_ctz((unsigned)n2));
       r = stdmin(pcol.x * s, 1.0); g = stdmin(pcol.y * s, 1.0); b = stdmin(pcol.z * s, 1.0);
@@ -1018,7 +1071,8 @@ __global__ void __launch_bounds__(kBlock, kWavesPerEU * 256 / kBlock) render_ker
     // RT_FLAG_GLOBAL_ROWS: the row's place in the whole frame (the buffer may be another GPU's,
     // mapped over xGMI: the shard's pixels land in the assembled frame as they finish)
     const int orow = P.out_global ? (P.stripe_count == 1 ? P.row_begin + lrow : stripe_row(P, lrow)) : lrow;
-    const size_t o = 3 * ((size_t)orow * P.W + px);
+    // (RAYS: the ray index, lrow its high and px its low 16 bits)
+    const size_t o = RAYS ? 3 * (((size_t)lrow << 16) | (size_t)px) : 3 * ((size_t)orow * P.W + px);
     // nontemporal (evict-first): the frame is written once and never read here, so its lines
     // should not push the path-state lines out of L2 (office: HBM writes 50.9 -> 45.5 MB per
     // frame, time unchanged; profiles/r03/write_traffic_r03.json)
@@ -1081,7 +1135,22 @@ __global__ void __launch_bounds__(kBlock, kWavesPerEU * 256 / kBlock) render_ker
       if (claims) {
         const long long wk = start + (group_log ? __popcll(m_claim & ((1ull << gbase) - 1ull)) : below(m_fetch));
         if (wk < g1) {
-          if (P.list) {   // adaptive pass: one sample of a listed pixel
+          if (RAYS) {   // ray wk of the caller's buffer; items past its end leave the lane idle
+            // the wave's items are consecutive from `start` (wave-uniform: taken to SGPRs for the resource)
+            const long long s0 = (long long)(((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(start >> 32)) << 32) |
+                                             (uint32_t)__builtin_amdgcn_readfirstlane((int)start));
+            const long long left = P.n_rays - s0;
+            const int nr = left < 64 ? (left > 0 ? (int)left : 0) : 64;
+            const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(
+                const_cast<rt_ray*>(P.rays + s0), 0, nr * (int)sizeof(rt_ray), kBufWord3);
+            if (wk < P.n_rays) {
+              px = (int)(wk & 0xffff);
+              lrow = (int)(wk >> 16);
+              sample = 0;
+              if (!start_ray(rr, (uint32_t)(wk - s0) * (uint32_t)sizeof(rt_ray)))   // degenerate: the background, lane still idle
+                store_pixel(add(d3(0, 0, 0), scl(1.0, d3(P.bg[0], P.bg[1], P.bg[2]))));
+            }
+          } else if (P.list) {   // adaptive pass: one sample of a listed pixel
             // (the divisors made opaque here: the compiler would otherwise keep their reciprocals in
             // registers across the whole persistent loop)
             long long ns = group_log ? 1 : P.nsamp;   // sample groups: one work item per listed pixel
@@ -1113,7 +1182,7 @@ __global__ void __launch_bounds__(kBlock, kWavesPerEU * 256 / kBlock) render_ker
             px = tx * kTileW + jx;
             lrow = (int)ty * kTileH + jy;
           }
-          if (px < P.W && lrow < P.rows) {
+          if (!RAYS && px < P.W && lrow < P.rows) {
             py = (P.stripe_count == 1)
                      ? P.row_begin + lrow
                      : stripe_row(P, lrow);
@@ -1446,7 +1515,11 @@ __global__ void __launch_bounds__(kBlock, kWavesPerEU * 256 / kBlock) render_ker
                       occluded = true;
                       break;
                     }
+#ifdef RT_RAY_LIST_PASS   // the t-limit may be the caller's tmax: a first hit at exactly tmax is none (a tie is one with a hit)
+                    if (t < tlim || (best != kNoHit && slot < best_slot)) {
+#else
                     if (t < tlim || slot < best_slot) {   // ties: smallest slot (mybvh.cpp:169 visit order)
+#endif
                       tlim = t;
                       best = (int)rec;
                       best_slot = slot;
@@ -2106,13 +2179,13 @@ __global__ void __launch_bounds__(kBlock, kWavesPerEU * 256 / kBlock) render_ker
         // sample groups: the colour waits in the (now free) ray slot for the group's ordered sum
         *R.o[0] = scol.x; *R.o[1] = scol.y; *R.o[2] = scol.z;
         state = ST_PARKED;
-      } else if (finish && P.list) {   // adaptive pass: this sample's trace() colour
+      } else if (finish && !RAYS && P.list) {   // adaptive pass: this sample's trace() colour
         const D3 c = scol;
         double* so = P.sample_out + 3 * (size_t)item;
         so[0] = c.x; so[1] = c.y; so[2] = c.z;
         state = heads_left > 0 ? ST_FETCH : ST_DONE;
       } else if (finish) {
-        if (P.tile_cost) {   // cost of this sample: its bounces, or in time mode the pixel's lifetime at its
+        if (!RAYS && P.tile_cost) {   // cost of this sample: its bounces, or in time mode the pixel's lifetime at its
                              // last sample, summed per tile position over the launch's frames
           const long long t = (long long)(lrow >> kTileHLog) * P.tiles_x + (px >> kTileWLog);   // tile position (all frames)
           uint32_t c = (uint32_t)(depth + 1);
@@ -2277,7 +2350,7 @@ __global__ void __launch_bounds__(kBlock, kWavesPerEU * 256 / kBlock) render_ker
       atomicAdd(&P.ctr[CD_BIG_LEAF_TESTS], r);
     }
   }
-  if (P.zero_map) {
+  if (!RAYS && P.zero_map) {
     // the next launch's work order, built by the first blocks to finish (their CUs would idle in the
     // drain): job h < 8 sorts head range h of order_src by cost, descending (stable: equal costs keep
     // the natural band order); jobs 8..15 clear an eighth of zero_map.  The block's LDS is free now.
@@ -2302,6 +2375,13 @@ __global__ void __launch_bounds__(kBlock, kWavesPerEU * 256 / kBlock) render_ker
     }
   }
 }
+
+#ifndef RT_RAY_LIST_PASS
+// the same kernel text once more, as radiance_kernel<RING> (this file, under whatever name a copy of
+// it is built: tools/build_ab.sh)
+#define RT_RAY_LIST_PASS 1
+#include __FILE_NAME__
+#undef RT_RAY_LIST_PASS
 
 // ---------------------------------------------------------------------------
 // Adaptive supersampling, selection step (adaptive_supersampling_device,
@@ -2487,15 +2567,18 @@ const Variant kVariants[] = {
     {render_kernel<4, false, false, 16>, false},
     {render_kernel<4, false, false, kShortStack, true>, false},
     {render_kernel<4, false, false, 16, true>, false},
+    {radiance_kernel<kShortStack>, false},   // [7] / [8] = [0] / [4] over a ray list (rt_trace_radiance)
+    {radiance_kernel<16>, false},
 };
-constexpr int kNumVariants = 7;
+constexpr int kNumVariants = 9;
+constexpr int kRayVariant = 7;   // + 1: the 16-entry ring
 // rt_upload_options.spp_lanes = 0: sample groups for spp > 1 launches or not
 constexpr bool kSppLanesDefault = true;   // config 3 +22.6 %, config 5 +19.3 % (r06d)
 // default group-size cap: 8K 64 spp at G = 32 (2 pixels per wave, 2 chunks each) +3.2 % over G = 64,
 // +0.7 % over G = 16; 4K 16 spp best at G = 16 = n^2 (r06o)
 constexpr int kGroupLanes = 32;
 constexpr int kRingDeep = 16;
-inline int variant_ring(int v) { return (v == 4 || v == 6) ? kRingDeep : kShortStack; }
+inline int variant_ring(int v) { return (v == 4 || v == 6 || v == kRayVariant + 1) ? kRingDeep : kShortStack; }
 // LDS per block: the variant's stack ring (ring entries per thread, at address 0: the kernel's
 // slot offsets are compile-time constants), kSlotDoubles doubles of slot, task + visibility words.
 size_t lds_bytes(int /*stack_words*/, int ring = kShortStack) {
@@ -2637,7 +2720,7 @@ const char* rt_last_error(void) { return g_error.c_str(); }
 
 const char* rt_build_info(void) {
   return "librt_hip: gfx950 persistent flattened render kernel; variants {4-wide 8-entry stack ring, 4-wide 16-entry ring (>= 2^18 triangle records), "
-         "4-wide+stats, 2-wide canonical stats, 4-wide+round timeline, sample groups (spp > 1) on both rings}; "
+         "4-wide+stats, 2-wide canonical stats, 4-wide+round timeline, sample groups (spp > 1) on both rings, ray lists (rt_trace_radiance) on both rings}; "
          "fp32 4-wide nodes (128 B) with an LDS treelet, "
          "fp64 triangles/shading, LDS ray slots + stack ring (global spill), global path state, 8 XCD work heads";
 }
@@ -2947,6 +3030,9 @@ int masked_stream(rt_scene* sc, hipStream_t caller, hipStream_t* out) {
 
 // One render launch; list != nullptr: adaptive pass over the pixel ids list[0 .. *count)
 // (at most list_cap of them) of the full frame.
+// rays != nullptr (rt_trace_radiance): the work items are the n_rays rays, outs[0] takes their
+// colours; p's camera is a 1 x 1 placeholder, its order flag RT_FLAG_NATURAL_ORDER, so the launch
+// neither reads nor writes the cost maps, the tile orders or the stream they are fenced on.
 // n_frames > 1 (rt_launch_frames): params p[0..n_frames) differ only in their camera vectors,
 // frame f is written to outs[f].
 // Has the work before event e finished?  hipErrorNotReady from the query is an answer, not a
@@ -2981,7 +3067,7 @@ bool use_groups(const rt_scene* sc, const rt_render_params* p) {
 
 int launch_render(rt_scene* sc, const rt_render_params* p, int n_frames, void* const* outs, rt_stats* stats,
                   void* stream, const uint32_t* list, const unsigned long long* count, long long list_cap,
-                  double* sample_out = nullptr) {
+                  double* sample_out = nullptr, const rt_ray* rays = nullptr, long long n_rays = 0) {
   if (!sc || !p || !outs) return fail(RT_ERR_INVALID, "rt_launch_compute_image: null argument");
   if (n_frames < 1 || n_frames > kMaxFrames) return fail(RT_ERR_INVALID, "rt_launch_frames: n_frames out of range");
   for (int f = 0; f < n_frames; ++f) {
@@ -3102,6 +3188,7 @@ int launch_render(rt_scene* sc, const rt_render_params* p, int n_frames, void* c
                        : (long long)P.tiles_x * ((rows + kTileH - 1) / kTileH);
   // (list mode: one list holds every frame's items, list_cap counts them all)
   P.n_tiles = list ? P.frame_tiles : P.frame_tiles * n_frames;
+  if (rays) P.n_tiles = P.frame_tiles = (n_rays + 63) / 64;   // 64 consecutive rays per wave-sized work unit
   if (P.n_tiles >= (1LL << 31)) return fail(RT_ERR_INVALID, "rt_launch: more than 2^31 tiles in one launch");
   P.div_row_tiles = div_magic((uint32_t)P.tiles_x * (uint32_t)n_frames);
   P.div_tiles_x = div_magic((uint32_t)P.tiles_x);
@@ -3109,7 +3196,7 @@ int launch_render(rt_scene* sc, const rt_render_params* p, int n_frames, void* c
   P.list = list;
   P.list_count = count;
   P.sample_out = sample_out;
-  if (!list && sc->d_tile_order && sc->tile_order_n == P.n_tiles) P.tile_order = sc->d_tile_order;
+  if (!list && !rays && sc->d_tile_order && sc->tile_order_n == P.n_tiles) P.tile_order = sc->d_tile_order;
   // cost-ordered work (one-frame launches): ordered by the costs of the launch before the previous
   // one of the same geometry, while this launch's costs are recorded
   // (several frames per launch: natural order and no cost map -- the same tile position of every
@@ -3118,7 +3205,7 @@ int launch_render(rt_scene* sc, const rt_render_params* p, int n_frames, void* c
   // one stream: implicit, so it never adds a cross-stream dependency; explicit RT_FLAG_COST_ORDER
   // also orders launches on other streams (each then waits for the previous launch's end).
   // Diagnostics, a debug order and RT_FLAG_NATURAL_ORDER keep the natural order.
-  const bool debug_order = sc->d_tile_order && sc->tile_order_n == P.n_tiles;
+  const bool debug_order = !rays && sc->d_tile_order && sc->tile_order_n == P.n_tiles;
   // (implicit: only on the stream of the last launch that touched the maps, so stream order fences
   // it against that launch's reads and its drain's writes of the maps -- whatever ran on other
   // streams in between)
@@ -3126,8 +3213,8 @@ int launch_render(rt_scene* sc, const rt_render_params* p, int n_frames, void* c
       !(p->flags & (RT_FLAG_TRAVERSAL_STATS | RT_FLAG_WIDE_STATS | RT_FLAG_TIMELINE | RT_FLAG_TILE_COST |
                     RT_FLAG_TILE_COST_TIME | RT_FLAG_NATURAL_ORDER)) &&
       !debug_order && (!sc->maps_used || sc->maps_stream == st);
-  const bool cost_debug = !list && (p->flags & (RT_FLAG_TILE_COST | RT_FLAG_TILE_COST_TIME));
-  const bool cost_order = !list && !group && n_frames == 1 && ((p->flags & RT_FLAG_COST_ORDER) || implicit_order);
+  const bool cost_debug = !list && !rays && (p->flags & (RT_FLAG_TILE_COST | RT_FLAG_TILE_COST_TIME));
+  const bool cost_order = !list && !rays && !group && n_frames == 1 && ((p->flags & RT_FLAG_COST_ORDER) || implicit_order);
   if (cost_order || cost_debug) {
     const long long n_pos = (long long)P.tiles_x * ((rows + kTileH - 1) / kTileH);
     if (sc->cost_cap < n_pos) {
@@ -3183,7 +3270,8 @@ int launch_render(rt_scene* sc, const rt_render_params* p, int n_frames, void* c
     }
   }
 
-  const int v = (p->flags & RT_FLAG_TRAVERSAL_STATS) ? 2
+  const int v = rays ? kRayVariant + (sc->deep ? 1 : 0)
+                : (p->flags & RT_FLAG_TRAVERSAL_STATS) ? 2
                 : (p->flags & RT_FLAG_WIDE_STATS) ? 1
                 : (p->flags & RT_FLAG_TIMELINE) ? 3
                 : sc->deep ? (group ? 6 : 4)   // the 16-entry-ring production variant
@@ -3249,6 +3337,10 @@ int launch_render(rt_scene* sc, const rt_render_params* p, int n_frames, void* c
     HIP_TRY(hipMemsetAsync(C.d_tl, 0, tb, st));
   }
   P.tl = C.d_tl;
+  if (rays) {   // (after the cost-order block: the two words alias tile_order and n_pos, null / unused here)
+    P.rays = rays;
+    P.n_rays = n_rays;
+  }
   if (rows > 0) {   // the launch's start / stop events travel with the kernel's dispatch (no marker packets)
     void* args[] = {&P};
     HIP_TRY(hipExtLaunchKernel(reinterpret_cast<const void*>(kVariants[v].fn), dim3((unsigned)blocks), dim3(kBlock),
@@ -3290,6 +3382,8 @@ int launch_render(rt_scene* sc, const rt_render_params* p, int n_frames, void* c
       unsigned long long n_list = 0;
       HIP_TRY(hipMemcpy(&n_list, count, sizeof n_list, hipMemcpyDeviceToHost));
       stats->pixels = (long long)std::min<unsigned long long>(n_list, (unsigned long long)std::max(0LL, list_cap));
+    } else if (rays) {
+      stats->pixels = n_rays;
     } else {
       stats->pixels = (long long)rows * p->camera.width * n_frames;
     }
@@ -3324,6 +3418,40 @@ extern "C" {
 
 int rt_launch_compute_image(rt_scene* sc, const rt_render_params* p, void* d_out, rt_stats* stats, void* stream) {
   return launch_render(sc, p, 1, &d_out, stats, stream, nullptr, nullptr, 0);
+}
+
+int rt_trace_radiance(rt_scene* sc, const rt_render_params* p, const rt_ray* d_rays, long long n, void* d_rgb,
+                      rt_stats* stats, void* stream) {
+  if (!sc || !p) return fail(RT_ERR_INVALID, "rt_trace_radiance: null scene or params");
+  if (n < 0) return fail(RT_ERR_INVALID, "rt_trace_radiance: negative ray count");
+  if (n > 0 && (!d_rays || !d_rgb)) return fail(RT_ERR_INVALID, "rt_trace_radiance: null ray or result buffer");
+  if (n > RT_RADIANCE_MAX_RAYS) return fail(RT_ERR_INVALID, "rt_trace_radiance: more than RT_RADIANCE_MAX_RAYS rays");
+  if (p->spp_n != 1) return fail(RT_ERR_INVALID, "rt_trace_radiance: spp_n must be 1 (one colour per ray)");
+  // (the defaults: every row of p's own camera, as rt_host_render_params fills them in)
+  if (p->row_begin != 0 || (p->row_end > 0 && p->row_end != p->camera.height) || p->stripe_count > 1 ||
+      p->stripe_index != 0)
+    return fail(RT_ERR_INVALID, "rt_trace_radiance: row ranges and stripes do not apply to a ray list");
+  if (p->out_format != RT_OUT_RGB_F32 && p->out_format != RT_OUT_RGB_F64)
+    return fail(RT_ERR_INVALID, "rt_trace_radiance: bad out_format");
+  if (p->flags & ~RT_FLAG_NATURAL_ORDER)
+    return fail(RT_ERR_INVALID, "rt_trace_radiance: only RT_FLAG_NATURAL_ORDER is accepted");
+  if (p->n_lights < 0 || p->n_lights > (p->lights_ext ? RT_LIGHTS_LIMIT : RT_MAX_LIGHTS))
+    return fail(RT_ERR_INVALID, "n_lights out of range (more than RT_MAX_LIGHTS lights need lights_ext)");
+  if (p->max_depth < 0) return fail(RT_ERR_INVALID, "max_depth must be >= 0");
+  if (n == 0) {
+    if (stats) std::memset(stats, 0, sizeof *stats);
+    return RT_OK;
+  }
+  // a render launch whose frame is the ray list: the camera is not read (a 1 x 1 placeholder for the
+  // launch's checks), and the natural order keeps it away from the cost maps and tile orders
+  rt_render_params q = *p;
+  q.camera = rt_camera{};
+  q.camera.width = q.camera.height = 1;
+  q.row_end = 0;
+  q.stripe_height = 1;
+  q.stripe_count = 1;
+  q.flags = RT_FLAG_NATURAL_ORDER;
+  return launch_render(sc, &q, 1, &d_rgb, stats, stream, nullptr, nullptr, 0, nullptr, d_rays, n);
 }
 
 int rt_launch_frames(rt_scene* sc, const rt_render_params* p, int n_frames, void* const* d_outs, rt_stats* stats,
@@ -3861,3 +3989,5 @@ void rt_scene_free(rt_scene* sc) {
 }
 
 }  // extern "C"
+
+#endif   // !RT_RAY_LIST_PASS (the part after the kernel)

@@ -435,6 +435,44 @@ class DeviceScene:
                 res = {k: v.numpy() for k, v in res.items()}
         return (res, st) if stats else res
 
+    def radiance(self, rays, params, stats=False, stream=None):
+        """Colours of the caller's rays (rt_trace_radiance): what a pixel whose one primary ray is
+        rays[i] would hold, shaded by the render kernel with params' lights, max_depth, background,
+        ambience and out_format (params.camera is ignored).  rays as for trace(): [n, 8] float64 rows
+        (o xyz, d xyz, tmax, reserved), a CUDA tensor on the scene's device, used in place, or a numpy
+        array, uploaded.  Returns [n, 3] of out_format's dtype -- tensors in, tensors out
+        (asynchronous on `stream`, an int pointer, None = the null stream, unless stats=True); numpy
+        in, numpy out.  stats=True returns (rgb, Stats).  A wave shades 64 consecutive rays: see
+        tile_major() for a camera's coherent order."""
+        import torch
+
+        try:   # (a partial RTAMD_HIP_LIB, built from an older source, may lack it)
+            fn = hip_lib().rt_trace_radiance
+        except AttributeError:
+            raise RtError("rt_trace_radiance: not exported by this librt_hip.so (RTAMD_HIP_LIB)") from None
+        host_in = isinstance(rays, np.ndarray)
+        dev = torch.device(f"cuda:{self.device}")
+        if host_in:
+            if rays.ndim != 2 or rays.shape[1] != 8:
+                raise ValueError("rays must be an [n, 8] float64 array")
+            rays = torch.from_numpy(np.ascontiguousarray(rays, dtype=np.float64)).to(dev)
+        if not (isinstance(rays, torch.Tensor) and rays.dtype == torch.float64 and rays.dim() == 2
+                and rays.shape[1] == 8 and rays.is_contiguous() and rays.device == dev):
+            raise ValueError(f"rays must be a contiguous [n, 8] float64 tensor on {dev}")
+        n = rays.shape[0]
+        dtype = torch.float64 if params.out_format == RT_OUT_RGB_F64 else torch.float32
+        out = torch.zeros((n, 3), dtype=dtype, device=dev)
+        st = abi.Stats() if stats else None
+        if stream:   # the buffers above were made on torch's current stream
+            torch.cuda.current_stream(dev).synchronize()
+        _check_hip(fn(self._h, C.byref(params), C.c_void_p(rays.data_ptr() if n else None), n,
+                      C.c_void_p(out.data_ptr() if n else None), C.byref(st) if st is not None else None,
+                      C.c_void_p(stream) if stream else None), "rt_trace_radiance")
+        if host_in:
+            torch.cuda.synchronize(dev)
+            out = out.cpu().numpy()
+        return (out, st) if stats else out
+
     def debug_counters(self):
         """Raw counter words of the last launch (see rt_debug_counters in rt_hip.h)."""
         buf = (C.c_ulonglong * 40)()
@@ -553,6 +591,41 @@ def camera_rays(params):
     rays[:, 3:6] = d.reshape(-1, 3)
     rays[:, 6] = np.inf
     return rays
+
+
+def panorama_rays(params, width, height):
+    """Rays of an equirectangular 360 x 180 degree camera at params.camera.eye for
+    DeviceScene.radiance / trace: [height * width, 8] float64 rows (o = eye, d, tmax = inf, reserved
+    0), row-major with row 0 at the bottom.  Pixel (x, y) looks along
+    d = cos(theta) sin(phi) right + sin(theta) up + cos(theta) cos(phi) forward with
+    phi = 2 pi (x + 0.5) / width - pi and theta = pi (y + 0.5) / height - pi / 2, where right and up
+    are the normalised x_dir and y_dir and forward is the normalised vector from the eye to the
+    image centre, lower_left + W/2 x_dir + H/2 y_dir - eye (W, H the camera's own size)."""
+    cam = params.camera
+    eye, ll = np.array(cam.eye[:]), np.array(cam.lower_left[:])
+    xd, yd = np.array(cam.x_dir[:]), np.array(cam.y_dir[:])
+    fwd = ll + 0.5 * cam.width * xd + 0.5 * cam.height * yd - eye
+    right, up, fwd = xd / np.linalg.norm(xd), yd / np.linalg.norm(yd), fwd / np.linalg.norm(fwd)
+    phi = (2.0 * np.pi * (np.arange(width) + 0.5) / width - np.pi)[None, :, None]
+    theta = (np.pi * (np.arange(height) + 0.5) / height - 0.5 * np.pi)[:, None, None]
+    d = np.cos(theta) * np.sin(phi) * right + np.sin(theta) * up + np.cos(theta) * np.cos(phi) * fwd
+    rays = np.zeros((height * width, 8))
+    rays[:, 0:3] = eye
+    rays[:, 3:6] = d.reshape(-1, 3)
+    rays[:, 6] = np.inf
+    return rays
+
+
+def tile_major(width, height):
+    """Permutation of range(height * width) that puts the rows of a row-major [height * width, ...]
+    array into the render kernel's tile order (rt_tile_shape: 8 x 8): tiles row by row from the
+    bottom-left one, a tile's pixels row-major and consecutive; the partial tiles at the right and
+    top edges hold the pixels they have.  rays[perm] is then coherent per wave of 64 for
+    DeviceScene.radiance / trace, and with inv = np.argsort(perm), rgb[inv] restores image order."""
+    tw, th = tile_shape()
+    ys, xs = np.meshgrid(np.arange(height), np.arange(width), indexing="ij")
+    key = ((ys // th) * ((width + tw - 1) // tw) + xs // tw) * (tw * th) + (ys % th) * tw + xs % tw
+    return np.argsort(key.ravel(), kind="stable")
 
 
 def camera_orbit(params, angle):
