@@ -467,6 +467,72 @@ int rt_trace_occluded(rt_scene* scene, const rt_ray* d_rays, long long n, unsign
 int rt_trace_radiance(rt_scene* scene, const rt_render_params* p, const rt_ray* d_rays, long long n,
                       void* d_rgb, rt_stats* stats, void* stream);
 
+/* Sorting caller-supplied rays into coherent waves.  rt_trace_closest,
+ * rt_trace_occluded and rt_trace_radiance put 64 consecutive rays in a wave, so the caller's ray
+ * order decides their speed.  rt_ray_order computes a coherence key per ray and the stable
+ * ascending order of the keys as a permutation; rt_permute_rows applies a permutation to rays
+ * (gather) and to result rows (scatter).  Results never depend on the order.
+ *   The key of a ray, 32 bits, for origin_bits ob in [0, 10] (-1 = 5) and db = min(15, (31 - 3 ob) / 2)
+ * direction bits: a degenerate ray (the queries' rule above) has RT_ORDER_KEY_DEGENERATE and sorts
+ * last; every other key is morton3(origin cell) << (2 db) | morton2(direction cell) < 2^31, with
+ * the origin cell floor((o - lo) / (hi - lo) * 2^ob) per axis, clamped to [0, 2^ob - 1] (0 on a flat
+ * axis), in the box of rt_scene_bounds, and the direction cell floor((p * 0.5 + 0.5) * 2^db), clamped to
+ * 2^db - 1, of the octahedral map p of d (csrc/device/rt_order_key.hpp is the definition). */
+#define RT_ORDER_MAX_RAYS (1LL << 31)
+#define RT_ORDER_KEY_DEGENERATE 0x80000000u
+/* The sort's tile: a block of rt_ray_order's sort owns a contiguous run of whole tiles of this
+ * many keys. */
+#define RT_ORDER_TILE 1024
+
+/* The box the keys quantise origins in: the scene's root box (the reference root's bounds
+ * widened by the layout's delta, what the kernels' entry test uses); zeros for a scene
+ * without triangles. */
+int rt_scene_bounds(const rt_scene* scene, double lo[3], double hi[3]);
+
+/* Pure host, no HIP call: bytes of d_workspace rt_ray_order needs for n rays
+ * (0 for n <= 0; non-decreasing in n):
+ *   3 * roundup(4 n, 256) + 4 * 256 * 1024
+ * = two key buffers and one index buffer (the sort's ping-pong; d_perm is the other index buffer)
+ * and the [digit][block] count table of at most 1024 blocks. */
+size_t rt_ray_order_workspace_bytes(long long n);
+
+/* Pure host, no HIP call, no scene: keys[i] of rays[i] (HOST pointers) in box [lo, hi].
+ * The same function text the device runs. */
+int rt_ray_keys_host(const double lo[3], const double hi[3], const rt_ray* rays, long long n,
+                     int origin_bits, unsigned int* keys);
+
+/* d_perm[j] = index of the ray that belongs at position j:
+ * the stable ascending order of the rays' keys.
+ * d_keys (optional, may be NULL): d_keys[i] = key of d_rays[i].
+ * Asynchronous on `stream`.
+ * No allocation, no host synchronisation and no scene state is touched.
+ * All scratch is the caller's d_workspace (rt_ray_order_workspace_bytes(n) bytes, 256-B aligned).
+ * Calls with different workspaces may therefore be in flight on different streams,
+ * beside renders and queries.
+ * n == 0: RT_OK, no launch.
+ * RT_ERR_INVALID, before any HIP call, for: a NULL scene; n < 0; n > RT_ORDER_MAX_RAYS; n > 0 with
+ * a NULL d_rays, d_perm or d_workspace; origin_bits outside [-1, 10]; n > 0 with a misaligned workspace.
+ * RT_ERR_HIP on a scene whose watchdog word is set (rt_scene_status). */
+int rt_ray_order(rt_scene* scene, const rt_ray* d_rays, long long n, int origin_bits,
+                 unsigned int* d_perm, unsigned int* d_keys, void* d_workspace, void* stream);
+
+/* inverse == 0 (gather):  dst row j       = src row perm[j].
+ * inverse != 0 (scatter): dst row perm[j] = src row j.
+ * j in [0, n); rows of row_bytes bytes, 1..256.
+ * An entry perm[j] >= n is skipped: nothing is read or written for it.
+ * Asynchronous on `stream` of `device`.
+ * d_src / d_dst must not overlap.
+ * Both must be aligned to the largest power of two <= 16 that divides row_bytes.
+ * RT_ERR_INVALID, before any HIP call, for: n < 0 or n > 2^32; row_bytes outside [1, 256]; a
+ * negative device; n > 0 with a NULL, misaligned or overlapping buffer.  n == 0: RT_OK, no launch. */
+int rt_permute_rows(const void* d_src, void* d_dst, const unsigned int* d_perm, long long n,
+                    int row_bytes, int inverse, int device, void* stream);
+
+/* Test hook in the style of the other rt_debug_* calls: caps the blocks of rt_ray_order's
+ * kernels on this scene (0 = default), so that a few thousand rays exercise blocks that own
+ * several tiles.  Never changes a result. */
+int rt_debug_set_order_grid(rt_scene* scene, int max_blocks);
+
 /* Cross-process access to a device buffer, for one process per GPU (the frame-assembly mode
  * RT_FLAG_GLOBAL_ROWS: every rank writes its stripes straight into rank 0's frame buffer).
  * rt_ipc_get_handle exports the device allocation that holds d_ptr (an RT_IPC_HANDLE_BYTES-byte

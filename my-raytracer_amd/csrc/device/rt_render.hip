@@ -2699,6 +2699,7 @@ struct rt_scene {
   hipStream_t masked_for[kMaskedStreams] = {};
   int n_masked = 0;
   QueryRing* query = nullptr;   // allocated by the scene's first ray query (rt_trace_closest / rt_trace_occluded)
+  int order_grid = 0;           // rt_debug_set_order_grid: block cap of rt_ray_order's sort (0: from n_cu)
 };
 
 namespace {
@@ -3413,6 +3414,8 @@ struct StreamScratch {
 
 // batched ray queries on the device scene: kernels, query contexts, rt_trace_closest / rt_trace_occluded
 #include "rt_query.inc"
+// sorting caller-supplied rays into coherent waves: rt_ray_order, rt_permute_rows
+#include "rt_order.inc"
 
 extern "C" {
 

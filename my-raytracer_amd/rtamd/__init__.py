@@ -391,14 +391,82 @@ class DeviceScene:
                                                C.byref(st)), "rt_render_to_host")
         return img, st
 
-    def trace(self, rays, occluded=False, stats=False, stream=None):
+    def bounds(self):
+        """(lo, hi) of the scene's root box (rt_scene_bounds): the box ray_order's keys quantise
+        origins in; zeros for a scene without triangles."""
+        lo, hi = (C.c_double * 3)(), (C.c_double * 3)()
+        _check_hip(_order_fn("rt_scene_bounds")(self._h, lo, hi), "rt_scene_bounds")
+        return np.array(lo[:]), np.array(hi[:])
+
+    def ray_order(self, rays, origin_bits=None, keys=False, stream=None):
+        """The coherent order of the caller's rays (rt_ray_order): perm, an int32 view of the uint32
+        result, with perm[j] = the index of the ray that belongs at position j -- the stable
+        ascending order of the rays' coherence keys (origin cell in bounds(), then octahedral
+        direction cell; origin_bits per axis 0..10, None = the library default of 5; degenerate rays
+        last).  rays as for trace(); keys=True returns (perm, keys), keys[i] the key of rays[i] as an
+        int32 view.  The workspace is a torch byte tensor.  Tensors in, tensors out (asynchronous on
+        `stream`, an int pointer, None = the null stream); numpy in, numpy out (uint32)."""
+        import torch
+
+        fn = _order_fn("rt_ray_order")
+        host_in = isinstance(rays, np.ndarray)
+        dev = torch.device(f"cuda:{self.device}")
+        if host_in:
+            if rays.ndim != 2 or rays.shape[1] != 8:
+                raise ValueError("rays must be an [n, 8] float64 array")
+            rays = torch.from_numpy(np.ascontiguousarray(rays, dtype=np.float64)).to(dev)
+        if not (isinstance(rays, torch.Tensor) and rays.dtype == torch.float64 and rays.dim() == 2
+                and rays.shape[1] == 8 and rays.is_contiguous() and rays.device == dev):
+            raise ValueError(f"rays must be a contiguous [n, 8] float64 tensor on {dev}")
+        n = rays.shape[0]
+        perm = torch.empty((n,), dtype=torch.int32, device=dev)
+        kt = torch.empty((n,), dtype=torch.int32, device=dev) if keys else None
+        work = torch.empty((order_workspace_bytes(n),), dtype=torch.uint8, device=dev)
+        if stream:   # the buffers above were made on torch's current stream
+            torch.cuda.current_stream(dev).synchronize()
+        _check_hip(fn(self._h, C.c_void_p(rays.data_ptr() if n else None), n,
+                      -1 if origin_bits is None else int(origin_bits), C.c_void_p(perm.data_ptr() if n else None),
+                      C.c_void_p(kt.data_ptr() if keys and n else None), C.c_void_p(work.data_ptr() if n else None),
+                      C.c_void_p(stream) if stream else None), "rt_ray_order")
+        if stream:   # the workspace returns to torch's allocator with this call
+            torch.cuda.ExternalStream(stream, device=dev).synchronize()
+        if host_in:
+            torch.cuda.synchronize(dev)
+            perm = perm.cpu().numpy().view(np.uint32)
+            kt = kt.cpu().numpy().view(np.uint32) if keys else None
+        return (perm, kt) if keys else perm
+
+    def _resolve_order(self, order, rays, stream):
+        """trace / radiance `order` argument -> int32 perm tensor on the device."""
+        import torch
+
+        n = rays.shape[0]
+        if isinstance(order, str):
+            if order != "auto":
+                raise ValueError('order must be None, "auto" or a permutation')
+            return self.ray_order(rays, stream=stream)
+        if isinstance(order, np.ndarray):
+            order = np.ascontiguousarray(order).astype(np.int64).astype(np.uint32).view(np.int32)   # uint32 entries
+            order = torch.from_numpy(order).to(rays.device)
+        if not (isinstance(order, torch.Tensor) and order.dtype == torch.int32 and order.dim() == 1
+                and order.shape[0] == n and order.is_contiguous() and order.device == rays.device):
+            raise ValueError(f"order must be a contiguous int32 tensor of {n} entries on {rays.device}")
+        return order
+
+    def trace(self, rays, occluded=False, stats=False, stream=None, order=None):
         """Batched ray query (rt_trace_closest / rt_trace_occluded).  rays: [n, 8] float64 rows
         (o xyz, d xyz, tmax, reserved) -- a CUDA tensor on the scene's device, used in place, or a
         numpy array, uploaded.  Closest hits come back as a dict of views of one [n, 8] float64
         result buffer (rt_hit rows): t, alpha, beta, normal [n, 3], and slot, mesh, prim as int32;
         occluded=True returns a uint8 array instead.  Tensors in, tensors out (asynchronous on
         `stream`, an int pointer, None = the null stream, unless stats=True); numpy in, numpy out.
-        stats=True returns (result, QueryStats)."""
+        stats=True returns (result, QueryStats).
+        order: None traces the rays in the caller's order.  "auto" sorts them into coherent waves
+        first (ray_order with the default bits), a permutation (ray_order's, or any int32 tensor /
+        integer array of n entries) uses that order: the rays are gathered, traced by the same entry
+        point and the result rows scattered back, so the values sit at the caller's indices and are
+        bit-identical to order=None.  With an order and a stream the call returns after the stream
+        has finished (the sorted copies are torch temporaries)."""
         import torch
 
         host_in = isinstance(rays, np.ndarray)
@@ -411,6 +479,10 @@ class DeviceScene:
                 and rays.shape[1] == 8 and rays.is_contiguous() and rays.device == dev):
             raise ValueError(f"rays must be a contiguous [n, 8] float64 tensor on {dev}")
         n = rays.shape[0]
+        perm = None
+        if order is not None:   # the rays in the order's sequence; the result rows go back below
+            perm = self._resolve_order(order, rays, stream)
+            rays = permute_rows(rays, perm, stream=stream)
         st = abi.QueryStats() if stats else None
         if occluded:
             out = torch.zeros((n,), dtype=torch.uint8, device=dev)
@@ -422,20 +494,22 @@ class DeviceScene:
             torch.cuda.current_stream(dev).synchronize()
         _check_hip(fn(self._h, C.c_void_p(rays.data_ptr() if n else None), n, C.c_void_p(out.data_ptr() if n else None),
                       C.byref(st) if st is not None else None, C.c_void_p(stream) if stream else None), what)
+        if perm is not None:
+            out = permute_rows(out, perm, inverse=True, stream=stream)
+            if stream:   # the sorted copies return to torch's allocator with this call
+                torch.cuda.ExternalStream(stream, device=dev).synchronize()
         if host_in:
             torch.cuda.synchronize(dev)
             out = out.cpu()
         if occluded:
             res = out.numpy() if host_in else out
         else:
-            ints = out.view(torch.int32)
-            res = {"t": out[:, 0], "alpha": out[:, 1], "beta": out[:, 2], "normal": out[:, 3:6],
-                   "slot": ints[:, 12], "mesh": ints[:, 13], "prim": ints[:, 14]}
+            res = _hit_views(out)
             if host_in:
                 res = {k: v.numpy() for k, v in res.items()}
         return (res, st) if stats else res
 
-    def radiance(self, rays, params, stats=False, stream=None):
+    def radiance(self, rays, params, stats=False, stream=None, order=None):
         """Colours of the caller's rays (rt_trace_radiance): what a pixel whose one primary ray is
         rays[i] would hold, shaded by the render kernel with params' lights, max_depth, background,
         ambience and out_format (params.camera is ignored).  rays as for trace(): [n, 8] float64 rows
@@ -443,7 +517,8 @@ class DeviceScene:
         array, uploaded.  Returns [n, 3] of out_format's dtype -- tensors in, tensors out
         (asynchronous on `stream`, an int pointer, None = the null stream, unless stats=True); numpy
         in, numpy out.  stats=True returns (rgb, Stats).  A wave shades 64 consecutive rays: see
-        tile_major() for a camera's coherent order."""
+        tile_major() for a camera's coherent order, and order ("auto" or a permutation, as for
+        trace()) for rays without an image grid: same bits, at the caller's indices."""
         import torch
 
         try:   # (a partial RTAMD_HIP_LIB, built from an older source, may lack it)
@@ -460,6 +535,10 @@ class DeviceScene:
                 and rays.shape[1] == 8 and rays.is_contiguous() and rays.device == dev):
             raise ValueError(f"rays must be a contiguous [n, 8] float64 tensor on {dev}")
         n = rays.shape[0]
+        perm = None
+        if order is not None:   # the rays in the order's sequence; the colours go back below
+            perm = self._resolve_order(order, rays, stream)
+            rays = permute_rows(rays, perm, stream=stream)
         dtype = torch.float64 if params.out_format == RT_OUT_RGB_F64 else torch.float32
         out = torch.zeros((n, 3), dtype=dtype, device=dev)
         st = abi.Stats() if stats else None
@@ -468,6 +547,10 @@ class DeviceScene:
         _check_hip(fn(self._h, C.byref(params), C.c_void_p(rays.data_ptr() if n else None), n,
                       C.c_void_p(out.data_ptr() if n else None), C.byref(st) if st is not None else None,
                       C.c_void_p(stream) if stream else None), "rt_trace_radiance")
+        if perm is not None:
+            out = permute_rows(out, perm, inverse=True, stream=stream)
+            if stream:   # the sorted copies return to torch's allocator with this call
+                torch.cuda.ExternalStream(stream, device=dev).synchronize()
         if host_in:
             torch.cuda.synchronize(dev)
             out = out.cpu().numpy()
@@ -520,6 +603,68 @@ class DeviceScene:
     def debug_corrupt_hierarchy(self):
         """Test hook (rt_debug_corrupt_hierarchy): the first 4-wide node becomes a cycle."""
         _check_hip(hip_lib().rt_debug_corrupt_hierarchy(self._h), "rt_debug_corrupt_hierarchy")
+
+
+def _hit_views(out):
+    """The dict of views trace() returns over one [n, 8] float64 tensor of rt_hit rows."""
+    import torch
+
+    ints = out.view(torch.int32)
+    return {"t": out[:, 0], "alpha": out[:, 1], "beta": out[:, 2], "normal": out[:, 3:6],
+            "slot": ints[:, 12], "mesh": ints[:, 13], "prim": ints[:, 14]}
+
+
+def _order_fn(name):
+    """An entry point of the ray-order feature (a partial RTAMD_HIP_LIB, built from an older source,
+    may lack it)."""
+    try:
+        return getattr(hip_lib(), name)
+    except AttributeError:
+        raise RtError(f"{name}: not exported by this librt_hip.so (RTAMD_HIP_LIB)") from None
+
+
+def order_workspace_bytes(n):
+    """Bytes of workspace rt_ray_order needs for n rays (rt_ray_order_workspace_bytes)."""
+    return int(_order_fn("rt_ray_order_workspace_bytes")(int(n)))
+
+
+def ray_keys_host(lo, hi, rays, origin_bits=None):
+    """The coherence keys of host rays ([n, 8] float64) in box [lo, hi], computed on the CPU by the
+    function the device runs (rt_ray_keys_host): uint32 [n]."""
+    rays = np.ascontiguousarray(rays, dtype=np.float64)
+    if rays.ndim != 2 or rays.shape[1] != 8:
+        raise ValueError("rays must be an [n, 8] float64 array")
+    keys = np.zeros(len(rays), dtype=np.uint32)
+    lo_c, hi_c = (C.c_double * 3)(*[float(x) for x in lo]), (C.c_double * 3)(*[float(x) for x in hi])
+    _check_hip(_order_fn("rt_ray_keys_host")(lo_c, hi_c, rays.ctypes.data_as(C.c_void_p), len(rays),
+                                             -1 if origin_bits is None else int(origin_bits),
+                                             keys.ctypes.data_as(C.POINTER(C.c_uint))), "rt_ray_keys_host")
+    return keys
+
+
+def permute_rows(src, perm, inverse=False, stream=None):
+    """Rows of a contiguous 1-D or 2-D CUDA tensor moved by a permutation (rt_permute_rows): a new
+    tensor dst with dst[j] = src[perm[j]], or with inverse=True dst[perm[j]] = src[j].  perm: a
+    contiguous int32 tensor (the uint32 entries of DeviceScene.ray_order) of src.shape[0] entries on
+    src's device; an entry >= n is skipped (its dst row stays zero).  A row is the bytes of src's
+    row stride, 1..256.  Asynchronous on `stream` (an int pointer, None = the null stream)."""
+    import torch
+
+    fn = _order_fn("rt_permute_rows")
+    if not (isinstance(src, torch.Tensor) and src.is_cuda and src.dim() in (1, 2) and src.is_contiguous()):
+        raise ValueError("src must be a contiguous 1-D or 2-D CUDA tensor")
+    n = src.shape[0]
+    if not (isinstance(perm, torch.Tensor) and perm.dtype == torch.int32 and perm.dim() == 1 and perm.shape[0] == n
+            and perm.is_contiguous() and perm.device == src.device):
+        raise ValueError(f"perm must be a contiguous int32 tensor of {n} entries on {src.device}")
+    row_bytes = (src.shape[1] if src.dim() == 2 else 1) * src.element_size()   # contiguous: the row stride
+    dst = torch.zeros_like(src)
+    if stream:   # dst was made on torch's current stream
+        torch.cuda.current_stream(src.device).synchronize()
+    _check_hip(fn(C.c_void_p(src.data_ptr() if n else None), C.c_void_p(dst.data_ptr() if n else None),
+                  C.c_void_p(perm.data_ptr() if n else None), n, int(row_bytes), 1 if inverse else 0,
+                  src.device.index or 0, C.c_void_p(stream) if stream else None), "rt_permute_rows")
+    return dst
 
 
 def tile_shape():

@@ -27,6 +27,9 @@ RT_FLAG_COST_ORDER = 32
 RT_FLAG_NATURAL_ORDER = 64
 RT_FLAG_GLOBAL_ROWS = 128
 RT_IPC_HANDLE_BYTES = 64
+RT_ORDER_MAX_RAYS = 1 << 31
+RT_ORDER_KEY_DEGENERATE = 0x80000000
+RT_ORDER_TILE = 1024
 RT_MULTI_GATHER = 0
 RT_MULTI_PEER = 1
 RT_MULTI_DEBUG_PEER_MISMATCH = 1
@@ -209,6 +212,15 @@ HIP_SYMBOLS = {
                                     C.c_void_p]),
     "rt_trace_radiance": (C.c_int, [C.c_void_p, C.POINTER(RenderParams), C.c_void_p, C.c_longlong, C.c_void_p,
                                     C.POINTER(Stats), C.c_void_p]),
+    "rt_scene_bounds": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "rt_ray_order_workspace_bytes": (C.c_size_t, [C.c_longlong]),
+    "rt_ray_keys_host": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p, C.c_longlong, C.c_int,
+                                   C.POINTER(C.c_uint)]),
+    "rt_ray_order": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                               C.c_void_p]),
+    "rt_permute_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_int,
+                                  C.c_void_p]),
+    "rt_debug_set_order_grid": (C.c_int, [C.c_void_p, C.c_int]),
     "rt_last_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "rt_tile_shape": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "rt_ipc_get_handle": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_ulonglong)]),
