@@ -533,6 +533,59 @@ int rt_permute_rows(const void* d_src, void* d_dst, const unsigned int* d_perm, 
  * several tiles.  Never changes a result. */
 int rt_debug_set_order_grid(rt_scene* scene, int max_blocks);
 
+/* Occlusion fans generated on the device: ambient occlusion, sky-view factor,
+ * hemispherical visibility.  rt_trace_ao traces k occlusion rays from each of n surface points and
+ * returns, per point, how many of them are NOT occluded; the rays exist only in registers, and no
+ * per-ray result is written.
+ *   A point is an rt_ray record: o = the surface point p, d = its normal nrm (any length > 0),
+ * tmax = the occlusion radius (+inf or DBL_MAX: unbounded).  A point is degenerate by the queries'
+ * rule: a non-finite component in o or d, dot(d, d) > 0 false, or tmax > 1e-5 false.
+ *   Fan ray s in [0, k) of a non-degenerate point i (csrc/device/rt_ao_fan.hpp is the definition;
+ * fp64, + - * / sqrt only, no contraction, so host and device agree bit for bit):
+ *     N = nrm / sqrt(dot(nrm, nrm))                    (the renderer's normalize)
+ *     sg = N.z >= 0 ? 1 : -1,  a = -1 / (sg + N.z),  b = N.x * N.y * a
+ *     T = (1 + sg * N.x * N.x * a, sg * b, -sg * N.x)     (the frame of Duff et al.)
+ *     B = (b, sg + N.y * N.y * a, -N.y)
+ *     set = hash((uint32_t)i ^ seed) % n_sets,  hash = the 32-bit mixer written out in the header
+ *     (lx, ly, lz) = d_dirs[(set * k + s) * 3 ..]      (the caller's local direction, z along N)
+ *     w = (lx * T + ly * B) + lz * N,  origin = p + bias * N          (per component)
+ * and the ray is Ray(origin, w) with the point's tmax, normalised and traced exactly as
+ * rt_trace_occluded would.  A degenerate point's fan rays are Ray(o, (0, 0, 0)): degenerate rays,
+ * never traversed and not occluded.  A local direction that makes w zero or non-finite gives such a
+ * ray too; nothing is clamped or rejected per direction. */
+#define RT_AO_MAX_SAMPLES 1024
+#define RT_AO_MAX_SETS 65536
+#define RT_AO_MAX_POINTS (1LL << 31)
+typedef struct rt_ao_params {
+  int k;              /* fan rays per point, 1..RT_AO_MAX_SAMPLES */
+  int n_sets;         /* direction sets, 1..RT_AO_MAX_SETS */
+  unsigned int seed;  /* picks each point's set */
+  int reserved_;
+  double bias;        /* finite; origin = p + bias * N */
+  const double* d_dirs; /* DEVICE, [n_sets][k][3] local directions, caller-owned */
+} rt_ao_params;
+
+/* d_unoccluded[i] = the number of point i's k fan rays that rt_trace_occluded reports as 0, i in
+ * [0, n) (device buffers), on `stream`:
+ *     d_unoccluded[i] == k - sum over s of occluded(rays[i * k + s]),  rays = rt_ao_rays_host's,
+ * for every point; a degenerate one reports k.  Asynchronous unless stats != NULL (then it
+ * synchronises the stream): rays = n * k, hits = the occluded fan rays, stack_spills and watchdog
+ * as for the queries.  It takes one of the scene's query contexts, so it may be in flight beside
+ * renders and queries on other streams; it allocates nothing beyond the contexts' first-use
+ * allocation and touches no scene state.  When 64 is not a multiple of k the counts are summed
+ * with integer atomics and the call zeroes d_unoccluded[0..n) on the stream first.  n == 0 returns
+ * RT_OK without a launch and touches nothing.
+ *   RT_ERR_INVALID, before any HIP call, for: a NULL scene or params; n < 0 or n >
+ * RT_AO_MAX_POINTS; k or n_sets out of range; a non-finite bias; n > 0 with a NULL d_points,
+ * d_dirs or d_unoccluded.  RT_ERR_HIP on a scene whose watchdog word is set (rt_scene_status). */
+int rt_trace_ao(rt_scene* scene, const rt_ray* d_points, long long n, const rt_ao_params* params,
+                unsigned int* d_unoccluded, rt_query_stats* stats, void* stream);
+
+/* Pure host, no HIP call, no scene: rays_out[i * k + s] = fan ray s of points[i] (HOST pointers,
+ * params->d_dirs a HOST pointer here), tmax = the point's, reserved_ = 0.  The same function text
+ * the device runs and the same argument checks. */
+int rt_ao_rays_host(const rt_ray* points, long long n, const rt_ao_params* params, rt_ray* rays_out);
+
 /* Cross-process access to a device buffer, for one process per GPU (the frame-assembly mode
  * RT_FLAG_GLOBAL_ROWS: every rank writes its stripes straight into rank 0's frame buffer).
  * rt_ipc_get_handle exports the device allocation that holds d_ptr (an RT_IPC_HANDLE_BYTES-byte

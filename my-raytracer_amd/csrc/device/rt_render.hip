@@ -3416,6 +3416,8 @@ struct StreamScratch {
 #include "rt_query.inc"
 // sorting caller-supplied rays into coherent waves: rt_ray_order, rt_permute_rows
 #include "rt_order.inc"
+// occlusion fans generated on the device: rt_trace_ao, rt_ao_rays_host
+#include "rt_ao.inc"
 
 extern "C" {
 

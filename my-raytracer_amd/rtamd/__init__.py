@@ -556,6 +556,55 @@ class DeviceScene:
             out = out.cpu().numpy()
         return (out, st) if stats else out
 
+    def ao(self, points, dirs, seed=0, bias=0.0, stats=False, stream=None):
+        """Occlusion fans generated on the device (rt_trace_ao): for each surface point the number
+        of its k fan rays that are NOT occluded, an int32 [n] result; divide by k for the open
+        fraction.  points: [n, 8] float64 rows (p xyz, normal xyz, radius as tmax, reserved) -- a
+        CUDA tensor on the scene's device, used in place, or a numpy array, uploaded; see
+        ao_points_from_hits.  dirs: [n_sets, k, 3] float64 local directions, z along the normal
+        (ao_directions), tensor or numpy likewise.  Point i uses set hash(i ^ seed) % n_sets and
+        starts its rays at p + bias * N.  The rays are those ao_rays_host writes out and each is
+        decided exactly as trace(..., occluded=True) decides it.  Tensors in, tensor out
+        (asynchronous on `stream`, an int pointer, None = the null stream, unless stats=True); numpy
+        points in, numpy out.  stats=True returns (counts, QueryStats): rays = n k, hits = the
+        occluded fan rays."""
+        import torch
+
+        fn = _ao_fn("rt_trace_ao")
+        host_in = isinstance(points, np.ndarray)
+        dev = torch.device(f"cuda:{self.device}")
+        if host_in:
+            if points.ndim != 2 or points.shape[1] != 8:
+                raise ValueError("points must be an [n, 8] float64 array")
+            points = torch.from_numpy(np.ascontiguousarray(points, dtype=np.float64)).to(dev)
+        dirs_uploaded = isinstance(dirs, np.ndarray)
+        if dirs_uploaded:
+            if dirs.ndim != 3 or dirs.shape[2] != 3:
+                raise ValueError("dirs must be an [n_sets, k, 3] float64 array")
+            dirs = torch.from_numpy(np.ascontiguousarray(dirs, dtype=np.float64)).to(dev)
+        if not (isinstance(points, torch.Tensor) and points.dtype == torch.float64 and points.dim() == 2
+                and points.shape[1] == 8 and points.is_contiguous() and points.device == dev):
+            raise ValueError(f"points must be a contiguous [n, 8] float64 tensor on {dev}")
+        if not (isinstance(dirs, torch.Tensor) and dirs.dtype == torch.float64 and dirs.dim() == 3
+                and dirs.shape[2] == 3 and dirs.is_contiguous() and dirs.device == dev):
+            raise ValueError(f"dirs must be a contiguous [n_sets, k, 3] float64 tensor on {dev}")
+        n = points.shape[0]
+        a = abi.AoParams(k=dirs.shape[1], n_sets=dirs.shape[0], seed=int(seed) & 0xffffffff, bias=float(bias),
+                         d_dirs=dirs.data_ptr() if dirs.numel() else None)
+        out = torch.zeros((n,), dtype=torch.int32, device=dev)
+        st = abi.QueryStats() if stats else None
+        if stream:   # the buffers above were made on torch's current stream
+            torch.cuda.current_stream(dev).synchronize()
+        _check_hip(fn(self._h, C.c_void_p(points.data_ptr() if n else None), n, C.byref(a),
+                      C.c_void_p(out.data_ptr() if n else None), C.byref(st) if st is not None else None,
+                      C.c_void_p(stream) if stream else None), "rt_trace_ao")
+        if stream and (host_in or dirs_uploaded):   # the uploaded copies return to torch's allocator with this call
+            torch.cuda.ExternalStream(stream, device=dev).synchronize()
+        if host_in:
+            torch.cuda.synchronize(dev)
+            out = out.cpu().numpy()
+        return (out, st) if stats else out
+
     def debug_counters(self):
         """Raw counter words of the last launch (see rt_debug_counters in rt_hip.h)."""
         buf = (C.c_ulonglong * 40)()
@@ -665,6 +714,86 @@ def permute_rows(src, perm, inverse=False, stream=None):
                   C.c_void_p(perm.data_ptr() if n else None), n, int(row_bytes), 1 if inverse else 0,
                   src.device.index or 0, C.c_void_p(stream) if stream else None), "rt_permute_rows")
     return dst
+
+
+def _ao_fn(name):
+    """An entry point of the occlusion-fan feature (a partial RTAMD_HIP_LIB, built from an older
+    source, may lack it)."""
+    try:
+        return getattr(hip_lib(), name)
+    except AttributeError:
+        raise RtError(f"{name}: not exported by this librt_hip.so (RTAMD_HIP_LIB)") from None
+
+
+def ao_rays_host(points, dirs, seed=0, bias=0.0):
+    """The fan rays DeviceScene.ao traces, written out on the CPU by the function the device runs
+    (rt_ao_rays_host): points [n, 8] and dirs [n_sets, k, 3] float64 numpy arrays -> [n * k, 8] rays
+    for DeviceScene.trace, ray i * k + s = sample s of point i."""
+    fn = _ao_fn("rt_ao_rays_host")
+    points = np.ascontiguousarray(points, dtype=np.float64)
+    dirs = np.ascontiguousarray(dirs, dtype=np.float64)
+    if points.ndim != 2 or points.shape[1] != 8:
+        raise ValueError("points must be an [n, 8] float64 array")
+    if dirs.ndim != 3 or dirs.shape[2] != 3:
+        raise ValueError("dirs must be an [n_sets, k, 3] float64 array")
+    n, k = len(points), dirs.shape[1]
+    rays = np.zeros((n * k, 8), dtype=np.float64)
+    a = abi.AoParams(k=k, n_sets=dirs.shape[0], seed=int(seed) & 0xffffffff, bias=float(bias),
+                     d_dirs=dirs.ctypes.data if dirs.size else None)
+    _check_hip(fn(points.ctypes.data_as(C.c_void_p) if n else None, n, C.byref(a),
+                  rays.ctypes.data_as(C.c_void_p) if n * k else None), "rt_ao_rays_host")
+    return rays
+
+
+def ao_directions(k, n_sets, seed=0, cosine=True):
+    """Direction sets for DeviceScene.ao: [n_sets, k, 3] float64 unit vectors of the hemisphere
+    z > 0, made on the host.  Each set holds k stratified samples -- sample j has its first
+    coordinate in stratum j of k and its second in a stratum drawn by a random permutation (one
+    sample per row and per column of the k x k grid) -- mapped cosine-weighted (density cos / pi:
+    the mean of the unoccluded fraction is then the ambient-occlusion integral) or, with
+    cosine=False, uniformly over the hemisphere (sky-view factor), and each set is rotated about z
+    by its own random angle."""
+    k, n_sets = int(k), int(n_sets)
+    if not (1 <= k <= abi.RT_AO_MAX_SAMPLES and 1 <= n_sets <= abi.RT_AO_MAX_SETS):
+        raise ValueError("k must be in [1, RT_AO_MAX_SAMPLES] and n_sets in [1, RT_AO_MAX_SETS]")
+    rng = np.random.default_rng(seed)
+    j = np.arange(k, dtype=np.float64)[None, :]
+    u = (j + rng.random((n_sets, k))) / k                                        # in [0, 1)
+    v = (rng.permuted(np.tile(np.arange(k, dtype=np.float64), (n_sets, 1)), axis=1) + rng.random((n_sets, k))) / k
+    phi = 2.0 * np.pi * (v + rng.random((n_sets, 1)))                            # the set's own rotation
+    if cosine:
+        z = np.sqrt(1.0 - u)
+        r = np.sqrt(u)
+    else:
+        z = 1.0 - u
+        r = np.sqrt(np.maximum(0.0, 1.0 - z * z))
+    d = np.stack([r * np.cos(phi), r * np.sin(phi), z], axis=2)
+    d[..., 2] = np.maximum(d[..., 2], 1e-9)                                       # z > 0 after rounding
+    return np.ascontiguousarray(d / np.sqrt((d * d).sum(axis=2, keepdims=True)))
+
+
+def ao_points_from_hits(rays, hits):
+    """Point records for DeviceScene.ao from the closest hits of rays, on the device: rays [n, 8]
+    float64 CUDA tensor, hits the dict DeviceScene.trace returned for it.  p = o + t * normalize(d),
+    the normal is the hit's, flipped to face the ray's origin, tmax = +inf (set column 6 for a finite
+    radius).  A ray that missed becomes a degenerate point (p = o, zero normal): it reports k."""
+    import torch
+
+    if not (isinstance(rays, torch.Tensor) and rays.is_cuda and rays.dtype == torch.float64 and rays.dim() == 2
+            and rays.shape[1] == 8):
+        raise ValueError("rays must be an [n, 8] float64 CUDA tensor")
+    t, nrm = hits["t"], hits["normal"]
+    hit = torch.isfinite(t)
+    d = rays[:, 3:6]
+    dn = d / torch.sqrt((d * d).sum(dim=1, keepdim=True))
+    p = rays[:, 0:3] + torch.where(hit, t, torch.zeros_like(t))[:, None] * torch.where(hit[:, None], dn, torch.zeros_like(dn))
+    facing = (nrm * d).sum(dim=1, keepdim=True) > 0.0
+    nrm = torch.where(facing, -nrm, nrm)
+    pts = torch.zeros_like(rays)
+    pts[:, 0:3] = torch.where(hit[:, None], p, rays[:, 0:3])
+    pts[:, 3:6] = torch.where(hit[:, None], nrm, torch.zeros_like(nrm))
+    pts[:, 6] = float("inf")
+    return pts
 
 
 def tile_shape():

@@ -30,6 +30,9 @@ RT_IPC_HANDLE_BYTES = 64
 RT_ORDER_MAX_RAYS = 1 << 31
 RT_ORDER_KEY_DEGENERATE = 0x80000000
 RT_ORDER_TILE = 1024
+RT_AO_MAX_SAMPLES = 1024
+RT_AO_MAX_SETS = 65536
+RT_AO_MAX_POINTS = 1 << 31
 RT_MULTI_GATHER = 0
 RT_MULTI_PEER = 1
 RT_MULTI_DEBUG_PEER_MISMATCH = 1
@@ -159,6 +162,12 @@ class QueryStats(C.Structure):
         return {name: int(getattr(self, name)) for name, _ in self._fields_ if name != "reserved_"}
 
 
+class AoParams(C.Structure):
+    """rt_ao_params: d_dirs is a device pointer for rt_trace_ao, a host pointer for rt_ao_rays_host."""
+    _fields_ = [("k", C.c_int), ("n_sets", C.c_int), ("seed", C.c_uint), ("reserved_", C.c_int),
+                ("bias", C.c_double), ("d_dirs", C.c_void_p)]
+
+
 class GenParams(C.Structure):
     _fields_ = [("width", C.c_int), ("height", C.c_int), ("n_triangles", C.c_longlong),
                 ("seed", C.c_ulonglong), ("max_depth", C.c_int), ("detail", C.c_int)]
@@ -221,6 +230,9 @@ HIP_SYMBOLS = {
     "rt_permute_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_int,
                                   C.c_void_p]),
     "rt_debug_set_order_grid": (C.c_int, [C.c_void_p, C.c_int]),
+    "rt_trace_ao": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.POINTER(AoParams), C.c_void_p,
+                              C.POINTER(QueryStats), C.c_void_p]),
+    "rt_ao_rays_host": (C.c_int, [C.c_void_p, C.c_longlong, C.POINTER(AoParams), C.c_void_p]),
     "rt_last_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "rt_tile_shape": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "rt_ipc_get_handle": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_ulonglong)]),
