@@ -254,8 +254,14 @@ typedef struct rt_upload_options {
                             other n, the diagnostic flags, tile-cost maps or RT_FLAG_COST_ORDER keep one lane
                             per pixel.  The adaptive pass follows it too (groups: no sample buffer, no
                             reduce kernel).  Pixels and ray counts are identical either way */
-  int reserved_[5];
+  int tree_opt;          /* subtree reinsertion on the finished binary hierarchy, before the wide collapse
+                            (DESIGN.md §20): 0 = by size (default): on for RT_TREE_SBVH from 2^10 to below 2^18
+                            input triangles (at most RT_TREE_OPT_PASSES passes), off otherwise; -1 = off;
+                            1..RT_TREE_OPT_MAX = at most this many passes, whatever the tree and the size */
+  int reserved_[4];
 } rt_upload_options;
+
+enum { RT_TREE_OPT_PASSES = 3, RT_TREE_OPT_MAX = 64 };
 
 /* Fills *opt with the defaults listed above. */
 void rt_upload_options_init(rt_upload_options* opt);
@@ -659,6 +665,34 @@ int rt_debug_last_grid(rt_scene* scene, long long* blocks, long long* full_block
  * box that holds every ray), so every production traversal that enters the hierarchy loops until
  * the kernel watchdog ends it.  Synchronises the device.  The scene is unusable afterwards. */
 int rt_debug_corrupt_hierarchy(rt_scene* scene);
+
+/* Diagnostics: what the device hierarchy of a scene would be, built on the host only (no HIP call,
+ * no device needed): the binary tree of opt->device_tree, optimised as opt->tree_opt says, and its
+ * 4-wide collapse.  Costs are relative to the root's surface area: sah_* = sum of the internal
+ * nodes' areas + sum of the leaves' areas x their records, dp_* = the collapse's dynamic programme
+ * at the root (collapse_c_tri per leaf slot, 1 per wide node), before and after the optimiser
+ * (equal when it is off).  invalid = 0, or RT_TREE_BAD_* bits of the final binary tree.  opt NULL =
+ * the defaults; opt->verbose also prints the optimiser's passes to stderr.  Returns RT_OK or the
+ * RT_ERR_* code rt_scene_upload_ex would return for these arguments. */
+enum {
+  RT_TREE_BAD_UNION = 1,    /* an internal box is not the union of its children's */
+  RT_TREE_BAD_LEAF = 2,     /* a leaf's box or records differ from the builder's */
+  RT_TREE_BAD_RECORDS = 4,  /* a device record is referenced by no leaf or by several, or leaf order breaks */
+  RT_TREE_BAD_IDS = 8,      /* a child id is not above its parent's, or a node is unreachable */
+  RT_TREE_BAD_FIXPOINT = 16 /* the optimiser's last pass moved nothing, yet running it again changed the tree */
+};
+typedef struct rt_tree_report {
+  long long binary_nodes, wide_nodes, records;
+  long long moved;          /* subtrees the optimiser moved */
+  double sah_before, sah_after, dp_before, dp_after;
+  double seconds;           /* the optimiser's time, renumbering included */
+  int passes;               /* passes run (0 = optimiser off) */
+  int stack4;               /* traversal-stack entries the 4-wide tree needs */
+  unsigned int invalid;
+  int converged;            /* 1: the last pass moved nothing (a fixed point; checked by a second run) */
+} rt_tree_report;
+int rt_debug_tree_report(const rt_scene_soa* soa, const rt_bvh_soa* bvh, const rt_upload_options* opt,
+                         rt_tree_report* out);
 
 /* Diagnostics: per-round timeline of the last launch with RT_FLAG_TIMELINE: for wave w of the
  * persistent grid and its r-th traversal round (r < 256), words [8(256w + r), +8) = {round start,

@@ -5,6 +5,8 @@
 //     reference leaves of more than kLeafMax triangles refined (RT_TREE_REFERENCE);
 //   * build_sah_tree: binned SAH over all triangles (RT_TREE_SAH);
 //   * build_sbvh_tree: binned SAH with spatial splits (RT_TREE_SBVH, the default);
+//   * tree_opt_passes / tree_opt_finish: subtree reinsertion on the finished binary tree
+//     (rt_upload_options.tree_opt);
 //   * build_image: 2-wide canonical nodes over the reference tree, the 4-wide collapse of the
 //     device tree (breadth-first treelet prefix, preorder below), conservative fp32 boxes
 //     (outward rounding + delta growth), fp64 triangle / shading records in device order.
@@ -25,6 +27,7 @@
 #include <sched.h>
 #include <string>
 #include <thread>
+#include <tuple>
 #include <vector>
 
 namespace rtk {
@@ -857,6 +860,284 @@ void build_sbvh_tree(const rt_scene_soa* s, const rt_upload_options& opt, DevTre
   tick("merge");
 }
 
+// ---- subtree reinsertion on a finished binary tree (rt_upload_options.tree_opt) ----
+// Insertion-based optimisation (Bittner, Hapala, Havran 2013): a pass takes every node that is
+// neither the root nor a child of it, largest box first, out of the tree together with its parent
+// (the sibling takes the parent's place), searches the remaining tree for the position where
+// putting it back adds the least surface area -- the new parent's box plus the growth of all boxes
+// above it --, and re-inserts it there through the freed parent node.  A subtree moves only if that
+// strictly lowers the summed area, so a converged tree is a fixed point.  Leaf boxes (the SBVH's
+// clipped reference boxes) are never touched; internal boxes stay exact unions of their children.
+// One thread, total orders everywhere: the result cannot depend on build_threads.
+// A search may open at most RT_TREE_OPT_SEARCH_CAP nodes: a safety bound on the build time of
+// hostile scenes, reached on none of the tested ones (the 65536-sliver tunnel, whose boxes all
+// overlap, gives the same tree at 4096 and 65536).  A search cut short takes the best position it
+// saw, which then depends on the order of equal-cost candidates: the fixed-point property holds for
+// searches that end by their bound (at a cap of 64 the office's second run still moves subtrees).
+#ifndef RT_TREE_OPT_SEARCH_CAP
+#define RT_TREE_OPT_SEARCH_CAP 4096
+#endif
+#ifndef RT_TREE_OPT_CHILD_ORDER
+#define RT_TREE_OPT_CHILD_ORDER 1     // A/B: 0 leaves children as reinsertion put them
+#endif
+constexpr long long kTreeOptMinTris = 1ll << 10;   // tree_opt "by size": on from this many input triangles
+constexpr double kTreeOptMinMove = 1e-12;   // a move must lower the local cost by this fraction (rounding guard)
+
+struct TreeOptStats {
+  int passes = 0;
+  long long moved = 0, moved_last = 0;
+  double seconds = 0.0;
+};
+
+inline double node_area(const DevTree& E, int n) { return half_area(E.lo[n], E.hi[n]); }
+inline double union_area(const DevTree& E, int a, int b) {
+  V3 lo = E.lo[a], hi = E.hi[a];
+  grow3(lo, hi, E.lo[b], E.hi[b]);
+  return half_area(lo, hi);
+}
+
+// Binary SAH cost (unnormalised): internal boxes once, leaf boxes once per record.
+double tree_sah(const DevTree& E) {
+  double c = 0.0;
+  for (size_t n = 0; n < E.left.size(); ++n) c += node_area(E, (int)n) * (E.count[n] > 0 ? (double)E.count[n] : 1.0);
+  return c;
+}
+
+// The SAH-optimal collapse's table (RT_COLLAPSE_SAH): D[n][j] = the least SAH cost of covering
+// binary subtree n with at most j child slots; a slot costs area * c_tri for a leaf and
+// area * c_node + D(children, 4) for a wide node (the 4 box tests of a visit are charged to
+// the visited node).  Children ids exceed their parent's in every builder (and after the
+// optimiser's renumbering), so one reverse sweep fills the table.
+struct CollapseDp {
+  std::vector<std::array<double, 5>> D;
+  std::vector<std::array<int8_t, 5>> Dk;   // 0: n itself is the slot, k > 0: k slots to the left child
+  std::vector<int8_t> Ik;                  // wide node n: slots given to its left child
+};
+void collapse_dp(const DevTree& E, double c_tri, CollapseDp& P) {
+  const size_t nn = E.left.size();
+  auto& D = P.D;
+  auto& Dk = P.Dk;
+  auto& Ik = P.Ik;
+  D.assign(nn, {0, 0, 0, 0, 0});
+  Dk.assign(nn, {0, 0, 0, 0, 0});
+  Ik.assign(nn, 0);
+  for (long long n = (long long)nn - 1; n >= 0; --n) {
+    if (E.count[n] != 0) {
+      for (int j = 1; j <= 4; ++j) D[n][j] = node_area(E, (int)n) * c_tri;
+      continue;
+    }
+    const int l = E.left[n], r = E.right[n];
+    double best = DBL_MAX;
+    for (int k = 1; k <= 3; ++k)
+      if (D[l][k] + D[r][4 - k] < best) { best = D[l][k] + D[r][4 - k]; Ik[n] = (int8_t)k; }
+    const double self = node_area(E, (int)n) + best;   // c_node = 1
+    D[n][1] = self;
+    for (int j = 2; j <= 4; ++j) {
+      D[n][j] = self;
+      for (int k = 1; k < j; ++k)
+        if (D[l][k] + D[r][j - k] < D[n][j]) { D[n][j] = D[l][k] + D[r][j - k]; Dk[n][j] = (int8_t)k; }
+    }
+  }
+}
+
+// Orders children, renumbers the tree in preorder (node 0 stays the root, every child id above its
+// parent's: the collapse's sweep needs it) and lays the records out in the leaves' left-to-right
+// order, so a subtree's records stay contiguous.
+void tree_opt_finish(DevTree& E, std::vector<uint32_t>& dev2slot) {
+  const size_t nn = E.left.size();
+#if RT_TREE_OPT_CHILD_ORDER
+  // The builders' children run low to high along their split axis, which the any-hit waves' "last
+  // hit slot first" order relies on: restore that along the axis where the centroids differ most.
+  for (size_t n = 0; n < nn; ++n) {
+    if (E.count[n] != 0) continue;
+    const int l = E.left[n], r = E.right[n];
+    double best = 0.0, diff = 0.0;
+    for (int k = 0; k < 3; ++k) {
+      const double d = (E.lo[r][k] + E.hi[r][k]) - (E.lo[l][k] + E.hi[l][k]);
+      if (std::fabs(d) > best) { best = std::fabs(d); diff = d; }
+    }
+    if (diff < 0.0) std::swap(E.left[n], E.right[n]);
+  }
+#endif
+  DevTree T;
+  T.resize(nn);
+  std::vector<uint32_t> recs(dev2slot.size());
+  size_t nrec = 0;
+  int next = 0;
+  std::vector<std::pair<int, int>> stk;   // (old id, new parent id or -1; right child flagged by ~parent)
+  stk.emplace_back(0, INT_MIN);
+  while (!stk.empty()) {
+    const auto [o, up] = stk.back();
+    stk.pop_back();
+    const int id = next++;
+    if (up != INT_MIN) (up < 0 ? T.right[~up] : T.left[up]) = id;
+    T.lo[id] = E.lo[o];
+    T.hi[id] = E.hi[o];
+    T.count[id] = E.count[o];
+    if (E.count[o] != 0) {
+      T.first[id] = (int)nrec;
+      for (int k = 0; k < E.count[o]; ++k) recs[nrec++] = dev2slot[(size_t)E.first[o] + k];
+    } else {
+      stk.emplace_back(E.right[o], ~id);
+      stk.emplace_back(E.left[o], id);
+    }
+  }
+  E = std::move(T);
+  dev2slot.swap(recs);
+}
+
+// Runs at most max_passes passes over E (children ids need not exceed their parent's afterwards:
+// tree_opt_finish renumbers).  Stops after a pass that moves nothing.
+void tree_opt_passes(DevTree& E, int max_passes, TreeOptStats& S) {
+  const size_t nn = E.left.size();
+  std::vector<int> parent(nn, -1);
+  for (size_t n = 0; n < nn; ++n)
+    if (E.count[n] == 0) parent[E.left[n]] = parent[E.right[n]] = (int)n;
+  std::vector<double> area(nn);
+  for (size_t n = 0; n < nn; ++n) area[n] = node_area(E, (int)n);
+  const double root_area = area[0];
+  auto refit_up = [&](int a) {   // boxes from a upwards as unions of their children, until one stays
+    for (; a >= 0; a = parent[a]) {
+      V3 lo = E.lo[E.left[a]], hi = E.hi[E.left[a]];
+      grow3(lo, hi, E.lo[E.right[a]], E.hi[E.right[a]]);
+      if (lo == E.lo[a] && hi == E.hi[a]) break;
+      E.lo[a] = lo;
+      E.hi[a] = hi;
+      area[a] = half_area(lo, hi);
+    }
+  };
+  auto replace_child = [&](int p, int from, int to) {
+    (E.left[p] == from ? E.left[p] : E.right[p]) = to;
+    parent[to] = p;
+  };
+  struct Cand { double induced; int id; };
+  auto later = [](const Cand& a, const Cand& b) { return a.induced != b.induced ? a.induced > b.induced : a.id > b.id; };
+  std::vector<Cand> heap;
+  std::vector<int> order, path;
+  double cost = tree_sah(E);
+  for (int pass = 1; pass <= max_passes; ++pass) {
+    order.clear();
+    for (size_t n = 1; n < nn; ++n)
+      if (parent[n] > 0) order.push_back((int)n);
+    std::sort(order.begin(), order.end(), [&](int a, int b) { return area[a] != area[b] ? area[a] > area[b] : a < b; });
+    long long moved = 0;
+    for (const int n : order) {
+      const int p = parent[n];
+      if (p <= 0) continue;   // became a child of the root earlier in this pass
+      const int g = parent[p];
+      const bool was_left = E.left[p] == n;
+      const int s = was_left ? E.right[p] : E.left[p];
+      replace_child(g, p, s);
+      refit_up(g);
+      const double an = area[n];
+      // the cost of the old position, summed in the search's order (root downwards)
+      path.clear();
+      for (int a = parent[s]; a >= 0; a = parent[a]) path.push_back(a);
+      double induced = 0.0;
+      for (size_t k = path.size(); k-- > 0;) induced += union_area(E, path[k], n) - area[path[k]];
+      const double old_cost = induced + union_area(E, s, n);
+      double best_cost = old_cost;
+      int best = s;
+      heap.clear();
+      heap.push_back({0.0, 0});
+      for (int opened = 0; !heap.empty() && opened < RT_TREE_OPT_SEARCH_CAP; ++opened) {
+        std::pop_heap(heap.begin(), heap.end(), later);
+        const Cand c = heap.back();
+        heap.pop_back();
+        if (c.induced + an >= best_cost) break;
+        const double direct = union_area(E, c.id, n);
+        if (c.id != 0 && c.induced + direct < best_cost) {   // (node 0 stays the root)
+          best_cost = c.induced + direct;
+          best = c.id;
+        }
+        if (E.count[c.id] != 0) continue;
+        const double below = c.induced + (direct - area[c.id]);
+        if (below + an < best_cost) {
+          heap.push_back({below, E.left[c.id]});
+          std::push_heap(heap.begin(), heap.end(), later);
+          heap.push_back({below, E.right[c.id]});
+          std::push_heap(heap.begin(), heap.end(), later);
+        }
+      }
+      if (!(best_cost < old_cost - kTreeOptMinMove * old_cost)) best = s;
+      // re-insert through the freed parent node p
+      const int up = parent[best];
+      replace_child(up, best, p);
+      if (best == s) {   // as it was
+        E.left[p] = was_left ? n : s;
+        E.right[p] = was_left ? s : n;
+      } else {
+        E.left[p] = best;
+        E.right[p] = n;
+        ++moved;
+      }
+      parent[best] = p;
+      parent[n] = p;
+      E.lo[p] = E.lo[best];
+      E.hi[p] = E.hi[best];
+      grow3(E.lo[p], E.hi[p], E.lo[n], E.hi[n]);
+      area[p] = half_area(E.lo[p], E.hi[p]);
+      refit_up(up);
+    }
+    S.passes = pass;
+    S.moved += moved;
+    S.moved_last = moved;
+    if (g_verbose) {
+      const double now = tree_sah(E);
+      std::fprintf(stderr, "  tree_opt: pass %d moved %lld subtrees, binary SAH cost %.4f -> %.4f\n", pass, moved,
+                   root_area > 0.0 ? cost / root_area : 0.0, root_area > 0.0 ? now / root_area : 0.0);
+      cost = now;
+    }
+    if (moved == 0) break;
+  }
+}
+
+// rt_debug_tree_report's checks.  A leaf's identity: its box and its records' reference slots.
+using LeafKey = std::tuple<V3, V3, std::vector<uint32_t>>;
+std::vector<LeafKey> leaf_keys(const DevTree& E, const std::vector<uint32_t>& dev2slot) {
+  std::vector<LeafKey> keys;
+  for (size_t n = 0; n < E.left.size(); ++n)
+    if (E.count[n] > 0)
+      keys.emplace_back(E.lo[n], E.hi[n],
+                        std::vector<uint32_t>(dev2slot.begin() + E.first[n], dev2slot.begin() + E.first[n] + E.count[n]));
+  std::sort(keys.begin(), keys.end());
+  return keys;
+}
+// RT_TREE_BAD_* of tree E over nrec records; `ordered`: the leaves' records must also follow each
+// other in left-to-right leaf order (what tree_opt_finish lays out).
+unsigned tree_invalid(const DevTree& E, size_t nrec, bool ordered) {
+  unsigned bad = 0;
+  const size_t nn = E.left.size();
+  std::vector<uint8_t> seen(nn, 0), used(nrec, 0);
+  std::vector<int> stk{0};
+  size_t reached = 0, next_rec = 0;
+  while (!stk.empty()) {
+    const int n = stk.back();
+    stk.pop_back();
+    if (n < 0 || (size_t)n >= nn || seen[n]) { bad |= RT_TREE_BAD_IDS; continue; }
+    seen[n] = 1;
+    ++reached;
+    if (E.count[n] != 0) {
+      if (E.first[n] < 0 || (size_t)E.first[n] + (size_t)E.count[n] > nrec) { bad |= RT_TREE_BAD_RECORDS; continue; }
+      if (ordered && (size_t)E.first[n] != next_rec) bad |= RT_TREE_BAD_RECORDS;
+      next_rec += (size_t)E.count[n];
+      for (int k = 0; k < E.count[n]; ++k)
+        if (used[(size_t)E.first[n] + k]++) bad |= RT_TREE_BAD_RECORDS;
+      continue;
+    }
+    const int l = E.left[n], r = E.right[n];
+    if (l <= n || r <= n || (size_t)l >= nn || (size_t)r >= nn) { bad |= RT_TREE_BAD_IDS; continue; }
+    V3 lo = E.lo[l], hi = E.hi[l];
+    grow3(lo, hi, E.lo[r], E.hi[r]);
+    if (lo != E.lo[n] || hi != E.hi[n]) bad |= RT_TREE_BAD_UNION;
+    stk.push_back(r);
+    stk.push_back(l);
+  }
+  if (reached != nn) bad |= RT_TREE_BAD_IDS;
+  for (size_t g = 0; g < nrec; ++g)
+    if (!used[g]) bad |= RT_TREE_BAD_RECORDS;
+  return bad;
+}
 
 int validate(const rt_scene_soa* s, const rt_bvh_soa* b) {
   if (!s || !b) return fail(RT_ERR_INVALID, "rt_scene_upload: null scene or bvh");
@@ -907,11 +1188,19 @@ static rt_upload_options options_by_size(rt_upload_options o, long long nt) {
   if (o.collapse == RT_COLLAPSE_BY_SIZE) o.collapse = RT_COLLAPSE_SAH;
   if (o.sbvh_alpha < 0.0) o.sbvh_alpha = deep ? 0.0 : kSbvhAlpha;
   if (o.sbvh_budget < 0.0) o.sbvh_budget = deep ? 1.5 : kSbvhBudget;
+  // subtree reinsertion: the default tree of the scenes it was measured on; the SAH and reference
+  // trees stay the un-optimised comparators they are.  Not below kTreeOptMinTris either: a tree that
+  // small is served from the LDS treelet, nothing was measured in its favour, and on the hostile
+  // split-stress scene (131 triangles) the any-hit rays tested 1 % more triangles
+  if (o.tree_opt == 0)
+    o.tree_opt = (o.device_tree == RT_TREE_SBVH && !deep && nt >= kTreeOptMinTris) ? RT_TREE_OPT_PASSES : -1;
   return o;
 }
 
 int build_image(const rt_scene_soa* s, const rt_bvh_soa* b, const rt_upload_options& opt_in, int bfs_top,
-                SceneImage& I) {
+                SceneImage& I, rt_tree_report* report) {
+  if (opt_in.tree_opt < -1 || opt_in.tree_opt > RT_TREE_OPT_MAX)
+    return fail(RT_ERR_INVALID, "rt_scene_upload: tree_opt must be -1, 0 or a pass count up to RT_TREE_OPT_MAX");
   const rt_upload_options opt = options_by_size(opt_in, s ? s->n_vertex_idx / 3 : 0);
   const int tree_kind = opt.device_tree;
   if (tree_kind != RT_TREE_SAH && tree_kind != RT_TREE_REFERENCE && tree_kind != RT_TREE_SBVH)
@@ -1006,6 +1295,74 @@ int build_image(const rt_scene_soa* s, const rt_bvh_soa* b, const rt_upload_opti
   tick("device tree");
   if (timing) std::fprintf(stderr, "rt_scene_upload: %lld triangles, %zu device records, %zu tree nodes\n", nt,
                            nt > 0 ? dev2slot.size() : (size_t)0, E.left.size());
+  // ---- subtree reinsertion (tree_opt), then children ordered, preorder ids, records re-laid ----
+  // The wide collapse's cost decides: an optimised tree whose 4-wide cost came out higher than the
+  // builder's (the binary cost never does) is dropped for the builder's.
+  CollapseDp P;
+  TreeOptStats ostats;
+  bool have_dp = false;
+  if (report) std::memset(report, 0, sizeof *report);
+  if (nt > 0 && (report || opt.tree_opt > 0)) {
+    const double ra = node_area(E, 0);
+    auto rel = [&](double c) { return ra > 0.0 ? c / ra : 0.0; };
+    collapse_dp(E, opt.collapse_c_tri, P);
+    const double dp0 = P.D[0][1], sah0 = tree_sah(E);
+    double dp1 = dp0, sah1 = sah0;
+    unsigned invalid = 0;
+    bool optimised = false;
+    have_dp = true;
+    if (opt.tree_opt > 0) {
+      const auto t0 = std::chrono::steady_clock::now();
+      DevTree E0 = E;
+      std::vector<uint32_t> d0 = dev2slot;
+      tree_opt_passes(E, opt.tree_opt, ostats);
+      tree_opt_finish(E, dev2slot);
+      collapse_dp(E, opt.collapse_c_tri, P);
+      dp1 = P.D[0][1];
+      sah1 = tree_sah(E);
+      ostats.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+      const bool kept = dp1 <= dp0;
+      optimised = kept;
+      if (report) {
+        if (leaf_keys(E, dev2slot) != leaf_keys(E0, d0)) invalid |= RT_TREE_BAD_LEAF;
+        if (kept && ostats.moved_last == 0) {   // a fixed point: a second run changes nothing
+          DevTree E2 = E;
+          std::vector<uint32_t> d2 = dev2slot;
+          TreeOptStats again;
+          tree_opt_passes(E2, 1, again);
+          tree_opt_finish(E2, d2);
+          if (again.moved != 0 || E2.lo != E.lo || E2.hi != E.hi || E2.left != E.left || E2.right != E.right ||
+              E2.first != E.first || E2.count != E.count || d2 != dev2slot)
+            invalid |= RT_TREE_BAD_FIXPOINT;
+        }
+      }
+      if (!kept) {
+        E = std::move(E0);
+        dev2slot = std::move(d0);
+        collapse_dp(E, opt.collapse_c_tri, P);
+        dp1 = dp0;
+        sah1 = sah0;
+        ostats.moved = 0;
+      }
+      if (timing)
+        std::fprintf(stderr, "  tree_opt: %d passes, %lld subtrees moved, 4-wide cost %.4f -> %.4f%s\n", ostats.passes,
+                     ostats.moved, rel(dp0), rel(P.D[0][1]), kept ? "" : " (dropped: the builder's tree is kept)");
+      tick("tree opt");
+    }
+    if (report) {
+      report->binary_nodes = (long long)E.left.size();
+      report->records = (long long)dev2slot.size();
+      report->moved = ostats.moved;
+      report->sah_before = rel(sah0);
+      report->sah_after = rel(sah1);
+      report->dp_before = rel(dp0);
+      report->dp_after = rel(dp1);
+      report->seconds = ostats.seconds;
+      report->passes = ostats.passes;
+      report->converged = ostats.passes > 0 && ostats.moved_last == 0;
+      report->invalid = invalid | tree_invalid(E, dev2slot.size(), optimised);
+    }
+  }
   // device records: one per triangle, or more where spatial splits duplicated references
   const long long nrec = nt > 0 ? (long long)dev2slot.size() : 0;
   if (nrec > (long long)kSlotMask) return fail(RT_ERR_UNSUPPORTED, "rt_scene_upload: more than 2^30 device records");
@@ -1022,39 +1379,12 @@ int build_image(const rt_scene_soa* s, const rt_bvh_soa* b, const rt_upload_opti
     };
     auto internal = [&](int c) { return E.count[c] == 0; };
     struct Kids { int c[4]; int n; };
-    // Optional SAH-optimal collapse (RT_COLLAPSE_SAH): D[n][j] = the least SAH cost of covering
-    // binary subtree n with at most j child slots; a slot costs area * c_tri for a leaf and
-    // area * c_node + D(children, 4) for a wide node (the 4 box tests of a visit are charged to
-    // the visited node).  Children ids exceed their parent's in every builder, so one reverse
-    // sweep fills the table.
+    // SAH-optimal collapse (RT_COLLAPSE_SAH): collapse_dp's table, kept from the optimiser's
+    // cost check where that ran.
     const bool dp = opt.collapse == RT_COLLAPSE_SAH;
-    const double c_tri = opt.collapse_c_tri;
-    std::vector<std::array<double, 5>> D;
-    std::vector<std::array<int8_t, 5>> Dk;   // 0: n itself is the slot, k > 0: k slots to the left child
-    std::vector<int8_t> Ik;                  // wide node n: slots given to its left child
-    if (dp) {
-      const size_t nn = E.left.size();
-      D.assign(nn, {0, 0, 0, 0, 0});
-      Dk.assign(nn, {0, 0, 0, 0, 0});
-      Ik.assign(nn, 0);
-      for (long long n = (long long)nn - 1; n >= 0; --n) {
-        if (!internal((int)n)) {
-          for (int j = 1; j <= 4; ++j) D[n][j] = area((int)n) * c_tri;
-          continue;
-        }
-        const int l = E.left[n], r = E.right[n];
-        double best = DBL_MAX;
-        for (int k = 1; k <= 3; ++k)
-          if (D[l][k] + D[r][4 - k] < best) { best = D[l][k] + D[r][4 - k]; Ik[n] = (int8_t)k; }
-        const double self = area((int)n) + best;   // c_node = 1
-        D[n][1] = self;
-        for (int j = 2; j <= 4; ++j) {
-          D[n][j] = self;
-          for (int k = 1; k < j; ++k)
-            if (D[l][k] + D[r][j - k] < D[n][j]) { D[n][j] = D[l][k] + D[r][j - k]; Dk[n][j] = (int8_t)k; }
-        }
-      }
-    }
+    if (dp && !have_dp) collapse_dp(E, opt.collapse_c_tri, P);
+    const auto& Dk = P.Dk;
+    const auto& Ik = P.Ik;
     auto kids_of = [&](int n) {   // open the largest internal child until 4 children
       if (dp) {
         Kids k{{-1, -1, -1, -1}, 0};
@@ -1163,6 +1493,11 @@ int build_image(const rt_scene_soa* s, const rt_bvh_soa* b, const rt_upload_opti
   tick("collapse4");
   if (depth > kMaxStackDepth || stack4 > kMaxStackDepth)
     return fail(RT_ERR_UNSUPPORTED, "rt_scene_upload: BVH needs more than 4096 traversal-stack entries");
+  if (report) {
+    report->wide_nodes = (long long)nodes4.size();
+    report->stack4 = stack4;
+    return RT_OK;
+  }
 
   // ---- triangle records / shading data in device order ----
   std::vector<uint8_t> last_dev((size_t)std::max<long long>(nrec, 1), 0);
@@ -1273,6 +1608,22 @@ void upload_options_defaults(rt_upload_options* o) {
   o->sbvh_budget = -1.0;   // by size
   o->sbvh_c_trav = 1.0;
   o->collapse_c_tri = 1.0;
+  o->tree_opt = 0;         // by size
 }
 
 }  // namespace rtk
+
+// Host only: no HIP call (rt_hip.h).  Zero fields that mean their defaults resolve as in
+// rt_scene_upload_ex.
+extern "C" int rt_debug_tree_report(const rt_scene_soa* soa, const rt_bvh_soa* bvh, const rt_upload_options* opt,
+                                    rt_tree_report* out) {
+  if (!out) return RT_ERR_INVALID;
+  rt_upload_options o, d;
+  rtk::upload_options_defaults(&d);
+  o = opt ? *opt : d;
+  if (o.sbvh_bins == 0) o.sbvh_bins = d.sbvh_bins;
+  if (o.sbvh_c_trav == 0.0) o.sbvh_c_trav = d.sbvh_c_trav;
+  if (o.collapse_c_tri == 0.0) o.collapse_c_tri = d.collapse_c_tri;
+  rtk::SceneImage none;
+  return rtk::build_image(soa, bvh, o, 0, none, out);
+}

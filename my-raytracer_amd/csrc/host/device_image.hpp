@@ -3,7 +3,7 @@
 // MI355X device layout (rt_layout.hpp) that librt_hip.so copies to each GPU.
 //
 // Pure C++ (no HIP): the device hierarchy builders (the reference tree with oversize leaves
-// refined, binned SAH, SAH with spatial splits), the 2-wide canonical nodes, the 4-wide
+// refined, binned SAH, SAH with spatial splits), their optimiser (subtree reinsertion), the 2-wide canonical nodes, the 4-wide
 // collapse with its breadth-first LDS treelet prefix, and the fp64 triangle / shading records
 // in device leaf order.  Built into librt_hip.so beside the kernel.
 #pragma once
@@ -38,9 +38,10 @@ struct SceneImage {
 
 // Builds the device layout.  `bfs_top`: how many 4-wide nodes to number breadth-first (the
 // treelet the kernel caches in LDS).  Returns RT_OK or an RT_ERR_* code with the message in
-// build_image_error().
+// build_image_error().  With `report` the call stops after the collapse (no records are built, I is
+// left alone) and fills it instead: rt_debug_tree_report.
 int build_image(const rt_scene_soa* s, const rt_bvh_soa* b, const rt_upload_options& opt, int bfs_top,
-                SceneImage& I);
+                SceneImage& I, rt_tree_report* report = nullptr);
 const std::string& build_image_error();
 
 // Defaults of rt_upload_options (include/rt_hip.h).

@@ -118,6 +118,22 @@ def upload_options(tree=None, **fields):
     return opt
 
 
+def tree_report(host_scene, tree=None, **options):
+    """rt_debug_tree_report of a prepared HostScene: the device hierarchy these upload options
+    give (tree_opt=-1 / 0 / n, ...), built on the host only -- no GPU needed.  Returns
+    abi.TreeReport (as_dict())."""
+    try:
+        fn = hip_lib().rt_debug_tree_report
+    except AttributeError:
+        raise RtError("rt_debug_tree_report: not exported by this librt_hip.so (RTAMD_HIP_LIB)") from None
+    opt = upload_options(tree, **options)
+    rep = abi.TreeReport()
+    rc = fn(host_scene.soa, host_scene.bvh, C.byref(opt), C.byref(rep))
+    if rc != RT_OK:
+        raise RtError(f"rt_debug_tree_report: error {rc}")
+    return rep
+
+
 def _np(ptr, count, dtype):
     if count == 0:
         return np.zeros(0, dtype=dtype)

@@ -180,8 +180,23 @@ class UploadOptions(C.Structure):
                 ("sbvh_bins", C.c_int), ("blocks_per_cu", C.c_int), ("grid_spare", C.c_int),
                 ("verbose", C.c_int), ("sbvh_alpha", C.c_double), ("sbvh_budget", C.c_double),
                 ("sbvh_c_trav", C.c_double), ("collapse_c_tri", C.c_double), ("reserve_cus", C.c_int),
-                ("order_window", C.c_int), ("spp_lanes", C.c_int),
-                ("reserved_", C.c_int * 5)]
+                ("order_window", C.c_int), ("spp_lanes", C.c_int), ("tree_opt", C.c_int),
+                ("reserved_", C.c_int * 4)]
+
+
+RT_TREE_OPT_PASSES, RT_TREE_OPT_MAX = 3, 64
+RT_TREE_BAD_UNION, RT_TREE_BAD_LEAF, RT_TREE_BAD_RECORDS, RT_TREE_BAD_IDS, RT_TREE_BAD_FIXPOINT = 1, 2, 4, 8, 16
+
+
+class TreeReport(C.Structure):
+    """rt_tree_report (rt_debug_tree_report): the device hierarchy as built on the host."""
+    _fields_ = [("binary_nodes", C.c_longlong), ("wide_nodes", C.c_longlong), ("records", C.c_longlong),
+                ("moved", C.c_longlong), ("sah_before", C.c_double), ("sah_after", C.c_double),
+                ("dp_before", C.c_double), ("dp_after", C.c_double), ("seconds", C.c_double),
+                ("passes", C.c_int), ("stack4", C.c_int), ("invalid", C.c_uint), ("converged", C.c_int)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
 
 
 RT_TREE_SAH, RT_TREE_REFERENCE, RT_TREE_SBVH = 0, 1, 2
@@ -247,6 +262,8 @@ HIP_SYMBOLS = {
     "rt_debug_blocks_per_cu": (C.c_int, [C.c_void_p, C.c_int]),
     "rt_debug_last_grid": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     "rt_debug_corrupt_hierarchy": (C.c_int, [C.c_void_p]),
+    "rt_debug_tree_report": (C.c_int, [C.POINTER(SceneSoA), C.POINTER(BvhSoA), C.POINTER(UploadOptions),
+                                       C.POINTER(TreeReport)]),
     "rt_scene_status": (C.c_int, [C.c_void_p]),
     "rt_scene_free": (None, [C.c_void_p]),
     "rt_last_error": (C.c_char_p, []),
