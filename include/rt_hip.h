@@ -592,6 +592,40 @@ int rt_trace_ao(rt_scene* scene, const rt_ray* d_points, long long n, const rt_a
  * the device runs and the same argument checks. */
 int rt_ao_rays_host(const rt_ray* points, long long n, const rt_ao_params* params, rt_ray* rays_out);
 
+/* Mean radiance of device-generated fans: light baking, irradiance probes, final
+ * gathering.  From each of n surface points the call traces the k fan rays of rt_trace_ao's
+ * definition above -- the same point records, the same rt_ao_params (k, n_sets, seed, bias, the
+ * device table d_dirs), built in registers by the same header text -- shades each one with the
+ * full render path, as rt_trace_radiance shades a caller's ray, and stores one mean colour per
+ * point; no ray and no per-ray colour is written.  The definition is compositional:
+ *     d_rgb[3*i + c] = (sum over s = 0 .. k-1 of R[i*k + s][c]) / (double)k
+ * where R is the RT_OUT_RGB_F64 result of rt_trace_radiance(scene, p, rt_ao_rays_host(points,
+ * fan), n * k, ...), the sum is taken in fp64 from +0.0 in increasing s, one addition per sample
+ * (no contraction, no pairwise order), followed by one fp64 division per channel; RT_OUT_RGB_F32
+ * stores (float) of that quotient.  The result equals that written-out computation bit for bit.
+ *   The mean is CLAMPED PER SAMPLE: each fan ray's colour is clamped to 1 per channel before it is
+ * added, which is what rt_trace_radiance returns for it.  An unclamped (HDR) sum and per-direction
+ * weights are not built.  A degenerate fan ray -- its point is degenerate, or the direction w is
+ * zero or non-finite -- contributes min(background, 1) and is not counted in primary_rays.  The
+ * point's tmax bounds each fan ray's primary segment only.
+ *   Read from p what rt_trace_radiance reads: the lights (inline or lights_ext), max_depth,
+ * background, ambience, out_format; p->camera is ignored.  RT_ERR_INVALID, before any HIP call,
+ * for everything rt_trace_radiance rejects about p (spp_n != 1, a row range or stripes, an unknown
+ * out_format, any flag but RT_FLAG_NATURAL_ORDER) and everything rt_trace_ao rejects about n, fan
+ * and the buffers (n < 0, n > RT_AO_MAX_POINTS, k or n_sets out of range, a non-finite bias, n > 0
+ * with a NULL d_points, d_dirs or d_rgb).  n == 0 returns RT_OK without a launch and touches
+ * nothing.  RT_ERR_HIP on a scene whose watchdog word is set.
+ *   It is a render launch, as rt_trace_radiance is: one of the scene's 8 launch contexts, the light
+ * table copied with the control block, reserve_cus / blocks_per_cu / grid_spare and the half-grid
+ * rule honoured (the persistent grid is sized from the lanes in use: a point's rays run on G =
+ * the largest power of two <= min(k, 32) neighbouring lanes, ceil(k / G) chunks of them), reported
+ * by rt_last_kernel_ms and rt_debug_last_grid; it neither reads nor records tile costs or orders.
+ *   Asynchronous unless stats != NULL (then it synchronises the stream): primary_rays = the fan
+ * rays traced (degenerate ones excluded), shadow_rays / reflection_rays as for renders -- all three
+ * equal the written-out rt_trace_radiance call's -- pixels = n, the counter-variant fields 0. */
+int rt_trace_gather(rt_scene* scene, const rt_render_params* p, const rt_ray* d_points, long long n,
+                    const rt_ao_params* fan, void* d_rgb, rt_stats* stats, void* stream);
+
 /* Cross-process access to a device buffer, for one process per GPU (the frame-assembly mode
  * RT_FLAG_GLOBAL_ROWS: every rank writes its stripes straight into rank 0's frame buffer).
  * rt_ipc_get_handle exports the device allocation that holds d_ptr (an RT_IPC_HANDLE_BYTES-byte
@@ -650,8 +684,8 @@ long long rt_debug_wave_log(rt_scene* scene, unsigned long long* out, long long 
 
 /* Diagnostics: persistent-grid blocks per CU of kernel variant 0 (production), 1 (4-wide
  * STATS), 2 (2-wide canonical STATS), 3 (timeline), 4 (production, 16-entry stack ring), 5 / 6
- * (0 / 4 with sample groups, spp > 1), 7 / 8 (0 / 4 over a ray list, rt_trace_radiance), as the
- * launches use it. */
+ * (0 / 4 with sample groups, spp > 1), 7 / 8 (0 / 4 over a ray list, rt_trace_radiance), 9 / 10
+ * (7 / 8 over surface points with fans, rt_trace_gather), as the launches use it. */
 int rt_debug_blocks_per_cu(rt_scene* scene, int variant);
 
 /* Diagnostics: the persistent grid (blocks) the last launch on the scene used, and the grid a

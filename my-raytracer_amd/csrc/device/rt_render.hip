@@ -39,8 +39,10 @@
 //
 // The kernel is compiled twice from its one text: as render_kernel (frames), and, through this
 // file including itself once below the kernel with RT_RAY_LIST_PASS set, as radiance_kernel
-// (rt_trace_radiance: the work items are a caller's rays).  Everything but the
-// kernel sits in the two #ifndef RT_RAY_LIST_PASS regions before and after it.
+// (rt_trace_radiance: the work items are a caller's rays), and a third time with
+// RT_FAN_PASS set as well, as gather_kernel (rt_trace_gather: the work items are surface points, each
+// shaded through a fan of rays built in registers on a sample group).  Everything but
+// the kernel sits in the two #ifndef RT_RAY_LIST_PASS regions before and after it.
 #ifndef RT_RAY_LIST_PASS
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -64,6 +66,8 @@
 #include "rt_layout.hpp"
 
 #pragma clang fp contract(off)
+
+#include "rt_ao_fan.hpp"   // the fan of a surface point (gather_kernel below, rt_ao.inc)
 
 using namespace rtk;
 
@@ -340,15 +344,30 @@ struct KParams {
   int rows;
   int tiles_x;
   int out_global;           // RT_FLAG_GLOBAL_ROWS: pixels go to their global row of a whole-frame buffer
-  int order_dilate;         // cost-ordered launches: cost window half-width along a tile row (order_range)
+  // (a fan launch, rt_trace_gather, is a ray-list launch whose list holds surface points; it has no
+  // pixel list, sample buffer or cost maps either, and its fan parameters take the places of five of
+  // those words -- the fan_* members of the unions below -- so the block keeps its layout)
+  union {
+    int order_dilate;       // cost-ordered launches: cost window half-width along a tile row (order_range)
+    uint32_t fan_seed;      // fan: picks each point's direction set (rt_ao_set)
+  };
   long long n_tiles;
   // list mode (adaptive pass): list entries are frame << 25 | local pixel id; work item w = one
   // sample (w % nsamp) of pixel list[w / nsamp] (a pixel's samples run on neighbouring lanes:
   // coherent rays); its trace() colour goes to sample_out[3w..3w+2] (summed in order later).
-  const uint32_t* list;
+  union {
+    const uint32_t* list;
+    const double* fan_dirs;    // fan: [fan_sets][fan_k][3] local directions
+  };
   const unsigned long long* list_count;
-  double* sample_out;
-  int nsamp;
+  union {
+    double* sample_out;
+    double fan_bias;           // fan: origin = p + bias * N
+  };
+  union {
+    int nsamp;
+    int fan_k;                 // fan: rays per point
+  };
   int n_prims;              // analytic primitives (0 unless rt_scene_set_analytic)
   const GPrim* prims;
   // frames of this launch (rt_launch_frames): work item w belongs to frame w / (64 * frame_tiles)
@@ -367,7 +386,10 @@ struct KParams {
     const rt_ray* rays;        // ray list: work item w is rays[w]
   };
   uint32_t* tile_cost;
-  int cost_time;            // tile_cost in 10-ns ticks of pixel lifetime instead of bounces
+  union {
+    int cost_time;          // tile_cost in 10-ns ticks of pixel lifetime instead of bounces
+    int fan_sets;           // fan: direction sets
+  };
   DivMagic div_row_tiles, div_tiles_x, div_stripe_h;   // n / (frames x tiles_x), n / tiles_x, n / stripe_h
   // cost-ordered launches: blocks whose work is done (the launch's drain, when CUs idle) build the
   // order of a later launch from a complete cost map and zero the map that launch will fill
@@ -788,15 +810,32 @@ __device__ void order_range(const uint32_t* cost, uint32_t* order, long long n_t
 // launch's one output buffer -- no tiles, frames, samples or cost maps; the ray index travels in
 // (px, lrow) as its low and high 16 bits (registers, donation word).  Always the production kernel:
 // 4-wide, no counters, no timeline, no sample groups.
+// FAN (the third pass, RT_FAN_PASS beside RT_RAY_LIST_PASS): a ray-list pass with sample groups.  Work
+// item w is surface point w of P.rays (o = the point, d = its normal, tmax = the fan rays' length
+// bound); its P.fan_k fan rays (rt_ao_fan.hpp) run as the samples of a group of G = 2^group_log <=
+// min(fan_k, 32) lanes, ceil(fan_k / G) chunks of them; every finished sample is clamped to 1 per
+// channel and parked, the group's first lane sums them in sample order, and their mean goes to 3 w.
+// RT_GROUPS_ON, "this launch runs sample groups", is the pass's own text: the size test the frame
+// kernels always had, and a constant here, where a fan of one ray is a group of one lane.  (A bool
+// computed once, or a lambda, instead of the macro moved the sample-group render kernels' register
+// allocation: 90 -> 94 SGPR spills; with the macro every earlier kernel's code is unchanged.)
 #ifndef RT_RAY_LIST_PASS
 template <int WIDTH, bool STATS, bool TL = false, int RING = kShortStack, bool GRP = false>
 __global__ void __launch_bounds__(kBlock, kWavesPerEU * 256 / kBlock) render_kernel(KParams P) {
-  constexpr bool RAYS = false;
-#else
+  constexpr bool RAYS = false, FAN = false;
+#define RT_GROUPS_ON group_log   // groups in use: a group size above one
+#elif !defined(RT_FAN_PASS)
 template <int RING>
 __global__ void __launch_bounds__(kBlock, kWavesPerEU * 256 / kBlock) radiance_kernel(KParams P) {
   constexpr int WIDTH = 4;
-  constexpr bool STATS = false, TL = false, GRP = false, RAYS = true;
+  constexpr bool STATS = false, TL = false, GRP = false, RAYS = true, FAN = false;
+#define RT_GROUPS_ON group_log
+#else
+template <int RING>
+__global__ void __launch_bounds__(kBlock, kWavesPerEU * 256 / kBlock) gather_kernel(KParams P) {
+  constexpr int WIDTH = 4;
+  constexpr bool STATS = false, TL = false, GRP = true, RAYS = true, FAN = true;
+#define RT_GROUPS_ON true   // always: a fan of one ray is a group of one lane (group_log = 0)
 #endif
   static_assert(RING >= kMigWords && (RING & (RING - 1)) == 0, "ring: a power of two holding the migration words");
   constexpr int kRingMask = RING - 1;
@@ -1052,6 +1091,48 @@ __global__ void __launch_bounds__(kBlock, kWavesPerEU * 256 / kBlock) radiance_k
     state = ST_CLOSEST;
     return true;
   };
+  // FAN: fan ray `sample` of the point whose index travels in (px, lrow), built in registers.  The
+  // 64-B point is read by its index with four 16-B loads (in bounds: the claim checked the index; a
+  // group's lanes read the same line) -- not through the refill's window, which exists at claim time
+  // only, while a group's later chunks start here too -- and the 24-B local direction through one
+  // bounded buffer over the whole table (below 2^31 bytes: rt_ao.inc's static_assert).  start_ray's
+  // degeneracy test is applied to (origin, w, tmax).  A degenerate sample is neither counted nor
+  // traversed, and contributes what a miss at depth 0 does, 0 + 1 * background: its lane gets a ray
+  // that nothing can hit (t-limit below every accepted t) and takes the miss path of SHADE, so a
+  // group never has all its lanes parked before SHADE has run.  A lane whose sample is past the fan's
+  // end (the last chunk when fan_k is no multiple of G) parks at once; the ordered sum skips it.
+  [[maybe_unused]] auto start_fan = [&]() {
+    if (sample >= P.fan_k) {
+      state = ST_PARKED;
+      return;
+    }
+    const size_t idx = ((size_t)lrow << 16) | (size_t)px;
+    const Q2* pq = reinterpret_cast<const Q2*>(P.rays + idx);
+    const Q2 q0 = pq[0], q1 = pq[1], q2 = pq[2], q3 = pq[3];
+    const uint32_t set = rt_ao_set((long long)idx, P.fan_seed, P.fan_sets);
+    const __amdgpu_buffer_rsrc_t dr = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<double*>(P.fan_dirs), 0, P.fan_sets * P.fan_k * 24, kBufWord3);
+    const uint32_t dvo = (set * (uint32_t)P.fan_k + (uint32_t)sample) * 24u;
+    const D2 l01 = buf_ld2(dr, dvo, 0);
+    const double l[3] = {l01.a, l01.b, buf_ld(dr, dvo + 16u, 0)};
+    const double pp[3] = {q0.x, q0.y, q1.x}, pn[3] = {q1.y, q2.x, q2.y};
+    const double tmax = q3.x;
+    double fo[3], fw[3];
+    rt_ao_fan_ray(pp, pn, tmax, l, P.fan_bias, fo, fw);
+    const D3 ro = d3(fo[0], fo[1], fo[2]);
+    const D3 dv = d3(fw[0], fw[1], fw[2]);
+    auto fin = [](double x) { return fabs(x) <= DBL_MAX; };   // false for NaN / inf
+    const bool ok = fin(ro.x) && fin(ro.y) && fin(ro.z) && fin(dv.x) && fin(dv.y) && fin(dv.z) &&
+                    sqrt(dot(dv, dv)) > 0.0 && tmax > 1e-5;   // NaN tmax: false
+    depth = 0;
+    if (ok) {
+      c_primary++;
+      emit_ray(ro, dv, tmax < DBL_MAX ? tmax : DBL_MAX);
+    } else {
+      emit_ray(d3(0.0, 0.0, 0.0), d3(0.0, 0.0, 1.0), -1.0);
+    }
+    state = ST_CLOSEST;
+  };
   // compute_image's last step for the pixel (px, lrow, frame): average the sum over the n x n
   // samples, clamp, store (mytracer_gpu.cu:155-159, 221-227)
   auto store_pixel = [&](D3 pcol) {
@@ -1059,7 +1140,10 @@ __global__ void __launch_bounds__(kBlock, kWavesPerEU * 256 / kBlock) radiance_k
     asm volatile("" : "+s"(n2));   // converted here, not hoisted into a VGPR live across the loop
     const double nn = (double)n2;
     double r, g, b;
-    if (RAYS) {   // one sample: no average
+    if (FAN) {   // the mean of the fan's samples, each clamped when it was parked: one division, no clamp
+      const double kk = (double)P.fan_k;
+      r = pcol.x / kk; g = pcol.y / kk; b = pcol.z / kk;
+    } else if (RAYS) {   // one sample: no average
       r = stdmin(pcol.x, 1.0); g = stdmin(pcol.y, 1.0); b = stdmin(pcol.z, 1.0);
     } else if ((n2 & (n2 - 1)) == 0) {
       // n2 = 2^k: x / n2 = x * 2^-k exactly (one rounding of the same exact value), no division
@@ -1106,9 +1190,9 @@ __global__ void __launch_bounds__(kBlock, kWavesPerEU * 256 / kBlock) radiance_k
     unsigned long long m_busy = wballot(state == ST_CLOSEST || state == ST_SHADOW || state >= ST_HSHADOW);
     // lanes that claim a work item: every idle lane, or (sample groups) the first lane of every idle
     // group, which claims a pixel for its G lanes
-    unsigned long long m_claim = group_log ? full_groups(m_fetch) : m_fetch;
+    unsigned long long m_claim = RT_GROUPS_ON ? full_groups(m_fetch) : m_fetch;
     const bool gate_open = !kRefillGate || m_busy == 0 || wballot(state == ST_SHADOW) == 0;   // wave-uniform
-    while (m_claim && gate_open && (group_log || __popcll(m_fetch) >= kRefill || m_busy == 0) && heads_left > 0) {
+    while (m_claim && gate_open && (RT_GROUPS_ON || __popcll(m_fetch) >= kRefill || m_busy == 0) && heads_left > 0) {
       const long long g0 = (n_tiles * head / kGroups) * 64;
       const long long g1 = (n_tiles * (head + 1) / kGroups) * 64;
       const int cnt = __popcll(m_claim);
@@ -1130,12 +1214,19 @@ __global__ void __launch_bounds__(kBlock, kWavesPerEU * 256 / kBlock) radiance_k
       }
       if (STATS) { w_refill = __builtin_amdgcn_s_memrealtime(); w_pixels += (unsigned long long)min((long long)cnt, g1 - start); }
       // this lane's item: its rank among the claiming lanes (sample groups: its group's rank)
-      const int gbase = group_log ? (lane & ~((1 << group_log) - 1)) : lane;
-      const bool claims = state == ST_FETCH && (!group_log || ((m_claim >> gbase) & 1ull) != 0ull);
+      const int gbase = RT_GROUPS_ON ? (lane & ~((1 << group_log) - 1)) : lane;
+      const bool claims = state == ST_FETCH && (!RT_GROUPS_ON || ((m_claim >> gbase) & 1ull) != 0ull);
       if (claims) {
-        const long long wk = start + (group_log ? __popcll(m_claim & ((1ull << gbase) - 1ull)) : below(m_fetch));
+        const long long wk = start + (RT_GROUPS_ON ? __popcll(m_claim & ((1ull << gbase) - 1ull)) : below(m_fetch));
         if (wk < g1) {
-          if (RAYS) {   // ray wk of the caller's buffer; items past its end leave the lane idle
+          if (FAN) {   // point wk for the group's lanes, lane l on fan ray l; items past the end leave them idle
+            if (wk < P.n_rays) {
+              px = (int)(wk & 0xffff);
+              lrow = (int)(wk >> 16);
+              sample = lane - gbase;
+              start_fan();
+            }
+          } else if (RAYS) {   // ray wk of the caller's buffer; items past its end leave the lane idle
             // the wave's items are consecutive from `start` (wave-uniform: taken to SGPRs for the resource)
             const long long s0 = (long long)(((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(start >> 32)) << 32) |
                                              (uint32_t)__builtin_amdgcn_readfirstlane((int)start));
@@ -1199,8 +1290,8 @@ __global__ void __launch_bounds__(kBlock, kWavesPerEU * 256 / kBlock) radiance_k
       }
       m_fetch = wballot(state == ST_FETCH);
       m_busy = wballot(state == ST_CLOSEST || state == ST_SHADOW || state >= ST_HSHADOW);
-      m_claim = group_log ? full_groups(m_fetch) : m_fetch;
-      if (!group_log && __popcll(m_fetch) < kRefill && m_busy != 0) break;
+      m_claim = RT_GROUPS_ON ? full_groups(m_fetch) : m_fetch;
+      if (!RT_GROUPS_ON && __popcll(m_fetch) < kRefill && m_busy != 0) break;
     }
     if (heads_left == 0 && state == ST_FETCH) state = ST_DONE;
     const bool busy = (state == ST_CLOSEST || state == ST_SHADOW || state >= ST_HSHADOW);
@@ -1862,7 +1953,7 @@ __global__ void __launch_bounds__(kBlock, kWavesPerEU * 256 / kBlock) radiance_k
 
     // ---- tail compaction: donate (sparse wave, queue empty) or adopt pooled lanes ----
     // (not with sample groups: a group's lanes and their parked colours stay in their wave)
-    if (heads_left == 0 && !group_log) {
+    if (heads_left == 0 && !RT_GROUPS_ON) {
       // wave in block, wave-uniform (an SGPR: derived at the use, not a VGPR held across the loop)
       const int wib = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
       const bool owner = (state == ST_CLOSEST || state == ST_SHADOW);
@@ -2175,8 +2266,10 @@ __global__ void __launch_bounds__(kBlock, kWavesPerEU * 256 / kBlock) radiance_k
           }
         }
       }
-      if (finish && group_log) {
+      if (finish && RT_GROUPS_ON) {
         // sample groups: the colour waits in the (now free) ray slot for the group's ordered sum
+        // (FAN: clamped here, per sample -- the colour rt_trace_radiance stores for this ray)
+        if (FAN) scol = d3(stdmin(scol.x, 1.0), stdmin(scol.y, 1.0), stdmin(scol.z, 1.0));
         *R.o[0] = scol.x; *R.o[1] = scol.y; *R.o[2] = scol.z;
         state = ST_PARKED;
       } else if (finish && !RAYS && P.list) {   // adaptive pass: this sample's trace() colour
@@ -2226,7 +2319,7 @@ __global__ void __launch_bounds__(kBlock, kWavesPerEU * 256 / kBlock) radiance_k
     // in sample order (the reference's (si, sj) order, mytracer_gpu.cu:202-221: sample s = si n + sj,
     // and a group holds samples chunk * G .. chunk * G + G - 1 on its lanes in order), then the group
     // starts its next chunk, or the pixel is stored and the group fetches another
-    if (group_log) {
+    if (RT_GROUPS_ON) {
       const unsigned long long full = full_groups(wballot(state == ST_PARKED));
       if (full != 0ull) {
         wave_lds_sync();   // the group's colours, written by its lanes in SHADE, are in LDS
@@ -2235,18 +2328,32 @@ __global__ void __launch_bounds__(kBlock, kWavesPerEU * 256 / kBlock) radiance_k
         const bool group_done = ((full >> gbase) & 1ull) != 0ull;
         if (group_done && lane == gbase) {
           D3 pc = sample == 0 ? d3(0, 0, 0) : LDV(R_PCOL);   // (the first lane holds sample chunk * G)
-          for (int k = 0; k < (1 << gl); ++k) {
-            const int t = wbase + gbase + k;
-            pc = add(pc, d3(lds_d[0 * kBlock + t], lds_d[1 * kBlock + t], lds_d[2 * kBlock + t]));
+          if constexpr (FAN) {   // the last chunk's lanes past the fan's end hold no sample
+            for (int k = 0; k < (1 << gl) && sample + k < P.fan_k; ++k) {
+              const int t = wbase + gbase + k;
+              pc = add(pc, d3(lds_d[0 * kBlock + t], lds_d[1 * kBlock + t], lds_d[2 * kBlock + t]));
+            }
+            if (sample + (1 << gl) < P.fan_k) STV(R_PCOL, pc);
+            else store_pixel(pc);
+          } else {
+            for (int k = 0; k < (1 << gl); ++k) {
+              const int t = wbase + gbase + k;
+              pc = add(pc, d3(lds_d[0 * kBlock + t], lds_d[1 * kBlock + t], lds_d[2 * kBlock + t]));
+            }
+            if (sample + (1 << gl) < P.spp_n * P.spp_n) STV(R_PCOL, pc);   // more chunks: the running sum
+            else store_pixel(pc);
           }
-          if (sample + (1 << gl) < P.spp_n * P.spp_n) STV(R_PCOL, pc);   // more chunks: the running sum
-          else store_pixel(pc);
         }
         wave_lds_sync();   // the first lane has read the group's slots before they take new rays
         if (group_done) {
           sample += 1 << gl;
-          if (sample < P.spp_n * P.spp_n) start_sample();
-          else state = heads_left > 0 ? ST_FETCH : ST_DONE;
+          if constexpr (FAN) {   // the group goes on while its first lane has a sample (the others may park at once)
+            if (sample - (lane - gbase) < P.fan_k) start_fan();
+            else state = heads_left > 0 ? ST_FETCH : ST_DONE;
+          } else {
+            if (sample < P.spp_n * P.spp_n) start_sample();
+            else state = heads_left > 0 ? ST_FETCH : ST_DONE;
+          }
         }
       }
     }
@@ -2375,12 +2482,17 @@ __global__ void __launch_bounds__(kBlock, kWavesPerEU * 256 / kBlock) radiance_k
     }
   }
 }
+#undef RT_GROUPS_ON
 
 #ifndef RT_RAY_LIST_PASS
 // the same kernel text once more, as radiance_kernel<RING> (this file, under whatever name a copy of
 // it is built: tools/build_ab.sh)
 #define RT_RAY_LIST_PASS 1
 #include __FILE_NAME__
+// ... and a third time, as gather_kernel<RING>: the ray-list pass with sample groups over device-built fans
+#define RT_FAN_PASS 1
+#include __FILE_NAME__
+#undef RT_FAN_PASS
 #undef RT_RAY_LIST_PASS
 
 // ---------------------------------------------------------------------------
@@ -2569,16 +2681,21 @@ const Variant kVariants[] = {
     {render_kernel<4, false, false, 16, true>, false},
     {radiance_kernel<kShortStack>, false},   // [7] / [8] = [0] / [4] over a ray list (rt_trace_radiance)
     {radiance_kernel<16>, false},
+    {gather_kernel<kShortStack>, false},   // [9] / [10] = [7] / [8] over surface points with fans (rt_trace_gather)
+    {gather_kernel<16>, false},
 };
-constexpr int kNumVariants = 9;
+constexpr int kNumVariants = 11;
 constexpr int kRayVariant = 7;   // + 1: the 16-entry ring
+constexpr int kFanVariant = 9;   // + 1: the 16-entry ring
 // rt_upload_options.spp_lanes = 0: sample groups for spp > 1 launches or not
 constexpr bool kSppLanesDefault = true;   // config 3 +22.6 %, config 5 +19.3 % (r06d)
 // default group-size cap: 8K 64 spp at G = 32 (2 pixels per wave, 2 chunks each) +3.2 % over G = 64,
 // +0.7 % over G = 16; 4K 16 spp best at G = 16 = n^2 (r06o)
 constexpr int kGroupLanes = 32;
 constexpr int kRingDeep = 16;
-inline int variant_ring(int v) { return (v == 4 || v == 6 || v == kRayVariant + 1) ? kRingDeep : kShortStack; }
+inline int variant_ring(int v) {
+  return (v == 4 || v == 6 || v == kRayVariant + 1 || v == kFanVariant + 1) ? kRingDeep : kShortStack;
+}
 // LDS per block: the variant's stack ring (ring entries per thread, at address 0: the kernel's
 // slot offsets are compile-time constants), kSlotDoubles doubles of slot, task + visibility words.
 size_t lds_bytes(int /*stack_words*/, int ring = kShortStack) {
@@ -2721,7 +2838,8 @@ const char* rt_last_error(void) { return g_error.c_str(); }
 
 const char* rt_build_info(void) {
   return "librt_hip: gfx950 persistent flattened render kernel; variants {4-wide 8-entry stack ring, 4-wide 16-entry ring (>= 2^18 triangle records), "
-         "4-wide+stats, 2-wide canonical stats, 4-wide+round timeline, sample groups (spp > 1) on both rings, ray lists (rt_trace_radiance) on both rings}; "
+         "4-wide+stats, 2-wide canonical stats, 4-wide+round timeline, sample groups (spp > 1) on both rings, ray lists (rt_trace_radiance) on both rings, "
+         "fans over surface points (rt_trace_gather) on both rings}; "
          "fp32 4-wide nodes (128 B) with an LDS treelet, "
          "fp64 triangles/shading, LDS ray slots + stack ring (global spill), global path state, 8 XCD work heads";
 }
@@ -3068,7 +3186,8 @@ bool use_groups(const rt_scene* sc, const rt_render_params* p) {
 
 int launch_render(rt_scene* sc, const rt_render_params* p, int n_frames, void* const* outs, rt_stats* stats,
                   void* stream, const uint32_t* list, const unsigned long long* count, long long list_cap,
-                  double* sample_out = nullptr, const rt_ray* rays = nullptr, long long n_rays = 0) {
+                  double* sample_out = nullptr, const rt_ray* rays = nullptr, long long n_rays = 0,
+                  const rt_ao_params* fan = nullptr) {
   if (!sc || !p || !outs) return fail(RT_ERR_INVALID, "rt_launch_compute_image: null argument");
   if (n_frames < 1 || n_frames > kMaxFrames) return fail(RT_ERR_INVALID, "rt_launch_frames: n_frames out of range");
   for (int f = 0; f < n_frames; ++f) {
@@ -3185,6 +3304,11 @@ int launch_render(rt_scene* sc, const rt_render_params* p, int n_frames, void* c
     while ((1 << (P.group_log + 1)) <= std::min(P.nsamp, gmax)) P.group_log++;
     P.chunks = P.nsamp >> P.group_log;
   }
+  if (fan) {   // a fan's rays are its point's samples: G = the largest power of two <= min(k, kGroupLanes)
+    P.group_log = 0;
+    while ((1 << (P.group_log + 1)) <= std::min(fan->k, kGroupLanes)) P.group_log++;
+    P.chunks = (fan->k + (1 << P.group_log) - 1) >> P.group_log;
+  }
   P.frame_tiles = list ? (list_cap * (group ? 1 : P.nsamp) + 63) / 64
                        : (long long)P.tiles_x * ((rows + kTileH - 1) / kTileH);
   // (list mode: one list holds every frame's items, list_cap counts them all)
@@ -3271,7 +3395,8 @@ int launch_render(rt_scene* sc, const rt_render_params* p, int n_frames, void* c
     }
   }
 
-  const int v = rays ? kRayVariant + (sc->deep ? 1 : 0)
+  const int v = fan ? kFanVariant + (sc->deep ? 1 : 0)
+                : rays ? kRayVariant + (sc->deep ? 1 : 0)
                 : (p->flags & RT_FLAG_TRAVERSAL_STATS) ? 2
                 : (p->flags & RT_FLAG_WIDE_STATS) ? 1
                 : (p->flags & RT_FLAG_TIMELINE) ? 3
@@ -3284,7 +3409,8 @@ int launch_render(rt_scene* sc, const rt_render_params* p, int n_frames, void* c
   P.top_off = (int)lds_bytes(sc->stack_words, ring);
   P.lights_off = P.top_off + n_top * (int)sizeof(GNode4);
   P.pool_off = P.lights_off + RT_MAX_LIGHTS * 6 * (int)sizeof(double);
-  const long long waves_needed = (P.n_tiles * 64 + 63) / 64;
+  // (a fan launch: the lanes its groups use, G per point)
+  const long long waves_needed = fan ? ((n_rays << P.group_log) + 63) / 64 : (P.n_tiles * 64 + 63) / 64;
   int bpc = sc->blocks_per_cu[v];
   if (sc->bpc_cap > 0) bpc = std::min(bpc, sc->bpc_cap);   // a smaller persistent grid (upload option)
   auto grid_of = [&](int bpc_) {
@@ -3341,6 +3467,13 @@ int launch_render(rt_scene* sc, const rt_render_params* p, int n_frames, void* c
   if (rays) {   // (after the cost-order block: the two words alias tile_order and n_pos, null / unused here)
     P.rays = rays;
     P.n_rays = n_rays;
+  }
+  if (fan) {   // (likewise: these alias the pixel list, the sample buffer and two cost-map words)
+    P.fan_dirs = fan->d_dirs;
+    P.fan_bias = fan->bias;
+    P.fan_k = fan->k;
+    P.fan_sets = fan->n_sets;
+    P.fan_seed = fan->seed;
   }
   if (rows > 0) {   // the launch's start / stop events travel with the kernel's dispatch (no marker packets)
     void* args[] = {&P};
@@ -3419,6 +3552,37 @@ struct StreamScratch {
 // occlusion fans generated on the device: rt_trace_ao, rt_ao_rays_host
 #include "rt_ao.inc"
 
+namespace {
+// what a ray-list launch (rt_trace_radiance, rt_trace_gather) rejects about its render parameters,
+// before any HIP call
+int ray_list_params_check(const char* name, const rt_render_params* p, const char* spp_rule) {
+  const std::string who = std::string(name) + ": ";
+  if (p->spp_n != 1) return fail(RT_ERR_INVALID, who + spp_rule);
+  // (the defaults: every row of p's own camera, as rt_host_render_params fills them in)
+  if (p->row_begin != 0 || (p->row_end > 0 && p->row_end != p->camera.height) || p->stripe_count > 1 ||
+      p->stripe_index != 0)
+    return fail(RT_ERR_INVALID, who + "row ranges and stripes do not apply to a ray list");
+  if (p->out_format != RT_OUT_RGB_F32 && p->out_format != RT_OUT_RGB_F64) return fail(RT_ERR_INVALID, who + "bad out_format");
+  if (p->flags & ~RT_FLAG_NATURAL_ORDER) return fail(RT_ERR_INVALID, who + "only RT_FLAG_NATURAL_ORDER is accepted");
+  if (p->n_lights < 0 || p->n_lights > (p->lights_ext ? RT_LIGHTS_LIMIT : RT_MAX_LIGHTS))
+    return fail(RT_ERR_INVALID, "n_lights out of range (more than RT_MAX_LIGHTS lights need lights_ext)");
+  if (p->max_depth < 0) return fail(RT_ERR_INVALID, "max_depth must be >= 0");
+  return RT_OK;
+}
+// a render launch whose frame is the ray list: the camera is not read (a 1 x 1 placeholder for the
+// launch's checks), and the natural order keeps it away from the cost maps and tile orders
+rt_render_params ray_list_params(const rt_render_params* p) {
+  rt_render_params q = *p;
+  q.camera = rt_camera{};
+  q.camera.width = q.camera.height = 1;
+  q.row_end = 0;
+  q.stripe_height = 1;
+  q.stripe_count = 1;
+  q.flags = RT_FLAG_NATURAL_ORDER;
+  return q;
+}
+}  // namespace
+
 extern "C" {
 
 int rt_launch_compute_image(rt_scene* sc, const rt_render_params* p, void* d_out, rt_stats* stats, void* stream) {
@@ -3431,32 +3595,28 @@ int rt_trace_radiance(rt_scene* sc, const rt_render_params* p, const rt_ray* d_r
   if (n < 0) return fail(RT_ERR_INVALID, "rt_trace_radiance: negative ray count");
   if (n > 0 && (!d_rays || !d_rgb)) return fail(RT_ERR_INVALID, "rt_trace_radiance: null ray or result buffer");
   if (n > RT_RADIANCE_MAX_RAYS) return fail(RT_ERR_INVALID, "rt_trace_radiance: more than RT_RADIANCE_MAX_RAYS rays");
-  if (p->spp_n != 1) return fail(RT_ERR_INVALID, "rt_trace_radiance: spp_n must be 1 (one colour per ray)");
-  // (the defaults: every row of p's own camera, as rt_host_render_params fills them in)
-  if (p->row_begin != 0 || (p->row_end > 0 && p->row_end != p->camera.height) || p->stripe_count > 1 ||
-      p->stripe_index != 0)
-    return fail(RT_ERR_INVALID, "rt_trace_radiance: row ranges and stripes do not apply to a ray list");
-  if (p->out_format != RT_OUT_RGB_F32 && p->out_format != RT_OUT_RGB_F64)
-    return fail(RT_ERR_INVALID, "rt_trace_radiance: bad out_format");
-  if (p->flags & ~RT_FLAG_NATURAL_ORDER)
-    return fail(RT_ERR_INVALID, "rt_trace_radiance: only RT_FLAG_NATURAL_ORDER is accepted");
-  if (p->n_lights < 0 || p->n_lights > (p->lights_ext ? RT_LIGHTS_LIMIT : RT_MAX_LIGHTS))
-    return fail(RT_ERR_INVALID, "n_lights out of range (more than RT_MAX_LIGHTS lights need lights_ext)");
-  if (p->max_depth < 0) return fail(RT_ERR_INVALID, "max_depth must be >= 0");
+  const int rc = ray_list_params_check("rt_trace_radiance", p, "spp_n must be 1 (one colour per ray)");
+  if (rc != RT_OK) return rc;
   if (n == 0) {
     if (stats) std::memset(stats, 0, sizeof *stats);
     return RT_OK;
   }
-  // a render launch whose frame is the ray list: the camera is not read (a 1 x 1 placeholder for the
-  // launch's checks), and the natural order keeps it away from the cost maps and tile orders
-  rt_render_params q = *p;
-  q.camera = rt_camera{};
-  q.camera.width = q.camera.height = 1;
-  q.row_end = 0;
-  q.stripe_height = 1;
-  q.stripe_count = 1;
-  q.flags = RT_FLAG_NATURAL_ORDER;
+  const rt_render_params q = ray_list_params(p);
   return launch_render(sc, &q, 1, &d_rgb, stats, stream, nullptr, nullptr, 0, nullptr, d_rays, n);
+}
+
+int rt_trace_gather(rt_scene* sc, const rt_render_params* p, const rt_ray* d_points, long long n,
+                    const rt_ao_params* fan, void* d_rgb, rt_stats* stats, void* stream) {
+  if (!sc || !p) return fail(RT_ERR_INVALID, "rt_trace_gather: null scene or params");
+  int rc = ray_list_params_check("rt_trace_gather", p, "spp_n must be 1 (the fan's rays are the samples)");
+  if (rc == RT_OK) rc = ao_check("rt_trace_gather", d_points, n, fan, d_rgb);
+  if (rc != RT_OK) return rc;
+  if (n == 0) {
+    if (stats) std::memset(stats, 0, sizeof *stats);
+    return RT_OK;
+  }
+  const rt_render_params q = ray_list_params(p);
+  return launch_render(sc, &q, 1, &d_rgb, stats, stream, nullptr, nullptr, 0, nullptr, d_points, n, fan);
 }
 
 int rt_launch_frames(rt_scene* sc, const rt_render_params* p, int n_frames, void* const* d_outs, rt_stats* stats,

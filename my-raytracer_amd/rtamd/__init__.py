@@ -621,6 +621,57 @@ class DeviceScene:
             out = out.cpu().numpy()
         return (out, st) if stats else out
 
+    def gather(self, points, dirs, params, seed=0, bias=0.0, stats=False, stream=None):
+        """Mean radiance of device-generated fans (rt_trace_gather): for each surface point the mean,
+        over its k fan rays, of the colour radiance() returns for that ray -- each clamped to 1 per
+        channel before it is added -- an [n, 3] result of params.out_format's dtype.  points, dirs,
+        seed and bias are ao()'s: [n, 8] float64 point records and [n_sets, k, 3] float64 local
+        directions, CUDA tensors on the scene's device, used in place, or numpy arrays, uploaded.
+        params gives the lights, max_depth, background, ambience and out_format (its camera is
+        ignored).  The result equals radiance(ao_rays_host(points, dirs, seed, bias), params) in
+        float64, summed per point in sample order and divided by k, bit for bit.  Tensors in, tensor
+        out (asynchronous on `stream`, an int pointer, None = the null stream, unless stats=True);
+        numpy points in, numpy out.  stats=True returns (rgb, Stats): primary_rays = the fan rays
+        traced, pixels = n."""
+        import torch
+
+        fn = _ao_fn("rt_trace_gather")
+        host_in = isinstance(points, np.ndarray)
+        dirs_uploaded = isinstance(dirs, np.ndarray)
+        dev = torch.device(f"cuda:{self.device}")
+        if host_in and (points.ndim != 2 or points.shape[1] != 8):
+            raise ValueError("points must be an [n, 8] float64 array")
+        if dirs_uploaded and (dirs.ndim != 3 or dirs.shape[2] != 3):
+            raise ValueError("dirs must be an [n_sets, k, 3] float64 array")
+        for name, x, dims, last in (("points", points, 2, 8), ("dirs", dirs, 3, 3)):
+            if isinstance(x, np.ndarray):
+                continue
+            if not (isinstance(x, torch.Tensor) and x.dtype == torch.float64 and x.dim() == dims
+                    and x.shape[-1] == last and x.is_contiguous() and x.device == dev):
+                shape = "[n, 8]" if dims == 2 else "[n_sets, k, 3]"
+                raise ValueError(f"{name} must be a contiguous {shape} float64 tensor on {dev}")
+        if host_in:
+            points = torch.from_numpy(np.ascontiguousarray(points, dtype=np.float64)).to(dev)
+        if dirs_uploaded:
+            dirs = torch.from_numpy(np.ascontiguousarray(dirs, dtype=np.float64)).to(dev)
+        n = points.shape[0]
+        a = abi.AoParams(k=dirs.shape[1], n_sets=dirs.shape[0], seed=int(seed) & 0xffffffff, bias=float(bias),
+                         d_dirs=dirs.data_ptr() if dirs.numel() else None)
+        dtype = torch.float64 if params.out_format == RT_OUT_RGB_F64 else torch.float32
+        out = torch.zeros((n, 3), dtype=dtype, device=dev)
+        st = abi.Stats() if stats else None
+        if stream:   # the buffers above were made on torch's current stream
+            torch.cuda.current_stream(dev).synchronize()
+        _check_hip(fn(self._h, C.byref(params), C.c_void_p(points.data_ptr() if n else None), n, C.byref(a),
+                      C.c_void_p(out.data_ptr() if n else None), C.byref(st) if st is not None else None,
+                      C.c_void_p(stream) if stream else None), "rt_trace_gather")
+        if stream and (host_in or dirs_uploaded):   # the uploaded copies return to torch's allocator with this call
+            torch.cuda.ExternalStream(stream, device=dev).synchronize()
+        if host_in:
+            torch.cuda.synchronize(dev)
+            out = out.cpu().numpy()
+        return (out, st) if stats else out
+
     def debug_counters(self):
         """Raw counter words of the last launch (see rt_debug_counters in rt_hip.h)."""
         buf = (C.c_ulonglong * 40)()

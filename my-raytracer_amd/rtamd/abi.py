@@ -248,6 +248,8 @@ HIP_SYMBOLS = {
     "rt_trace_ao": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.POINTER(AoParams), C.c_void_p,
                               C.POINTER(QueryStats), C.c_void_p]),
     "rt_ao_rays_host": (C.c_int, [C.c_void_p, C.c_longlong, C.POINTER(AoParams), C.c_void_p]),
+    "rt_trace_gather": (C.c_int, [C.c_void_p, C.POINTER(RenderParams), C.c_void_p, C.c_longlong, C.POINTER(AoParams),
+                                  C.c_void_p, C.POINTER(Stats), C.c_void_p]),
     "rt_last_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "rt_tile_shape": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "rt_ipc_get_handle": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_ulonglong)]),
