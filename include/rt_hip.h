@@ -44,7 +44,7 @@ extern "C" {
 #define RT_OK 0
 #define RT_ERR_INVALID (-1)     /* bad argument / inconsistent scene */
 #define RT_ERR_HIP (-2)         /* HIP runtime failure */
-#define RT_ERR_UNSUPPORTED (-3) /* scene exceeds a compiled limit (e.g. BVH depth) */
+#define RT_ERR_UNSUPPORTED (-3) /* scene exceeds a compiled limit (e.g. BVH depth, RT_MAX_COORDINATE) */
 
 /* Lights held inline in rt_render_params (and staged in LDS by the kernel).  Scenes with
  * more lights pass them through rt_render_params.lights_ext (any count up to
@@ -179,8 +179,25 @@ typedef struct rt_stats {
 
 typedef struct rt_scene rt_scene;   /* opaque device-resident scene */
 
+/* Largest vertex coordinate magnitude a scene may hold: 2^61, about 2.3e18 (see rt_scene_upload). */
+#define RT_MAX_COORDINATE 2305843009213693952.0
+
 /* Uploads the scene to HIP device `device` (hipSetDevice), converting the
- * host SoA + reference BVH into the MI355X layout.  Leaves the device current. */
+ * host SoA + reference BVH into the MI355X layout.  Leaves the device current.
+ *
+ * Supported coordinate range (derivation: DESIGN.md §4, "Supported coordinate range").  Results do
+ * not depend on the scene's scale or position: the fp32 boxes grow by 2^-20 max|vertex|, a relative
+ * amount.  The only absolute limit is fp32's range: the 4-wide kernels multiply the ray origin,
+ * moved into the root box, by a reciprocal direction clamped at 1e20, which overflows from
+ * max|vertex| = 3.4e18 on.  A scene whose max|vertex| exceeds RT_MAX_COORDINATE is refused with
+ * RT_ERR_UNSUPPORTED (one infinite coordinate included), whatever else it holds.  NaN coordinates are
+ * not looked for: the reference box of their triangles excludes them and those triangles are never
+ * hit.  Small scenes need no limit of this kind, but the reference's own absolute constants
+ * (|S| < 1e-10 rejects a triangle, t <= 1e-5 a hit) empty a scene shrunk by about 2^-20.
+ * Ray origins (camera eyes, lights, rt_ray origins) may lie far outside the scene: each ray enters
+ * the root box at a point computed in fp64, whose rounding error, about 6 * 2^-53 times the origin's
+ * distance D, stays inside the part of the box growth the fp32 error bound leaves free while
+ * D <= 2^28 max|vertex|. */
 int rt_scene_upload(const rt_scene_soa* soa, const rt_bvh_soa* bvh, int device, rt_scene** out);
 
 /* Device traversal hierarchy (never changes a pixel or a ray count: the closest hit is

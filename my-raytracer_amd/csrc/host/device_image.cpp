@@ -1227,6 +1227,14 @@ int build_image(const rt_scene_soa* s, const rt_bvh_soa* b, const rt_upload_opti
   double M = 0.0;
   for (long long k = 0; k < 3LL * s->n_vertices; ++k) M = std::max(M, std::fabs(s->vertex_pos[k]));
   if (!(M > 0.0)) M = 1.0;
+  // The 4-wide kernels form o * inv in fp32 with |o| <= M + delta (the origin is moved into the root
+  // box) and |inv| up to 1e20 (the reciprocal clamp of an axis-parallel ray): above M = 3.4e18 the
+  // product overflows and such a ray misses every box (supported coordinate range).
+  if (M > RT_MAX_COORDINATE) {
+    char msg[160];
+    std::snprintf(msg, sizeof msg, "rt_scene_upload: vertex coordinate of magnitude %.3g beyond the supported 2^61 (2.3e18)", M);
+    return fail(RT_ERR_UNSUPPORTED, msg);
+  }
   const double delta = M * 9.5367431640625e-07;   // 2^-20
 
   // ---- 2-wide fp32 nodes in preorder ----

@@ -11,6 +11,7 @@ RT_OK = 0
 RT_ERR_INVALID = -1
 RT_ERR_HIP = -2
 RT_ERR_UNSUPPORTED = -3
+RT_MAX_COORDINATE = 2.0 ** 61   # largest vertex coordinate magnitude rt_scene_upload takes
 RT_MAX_LIGHTS = 16
 RT_LIGHTS_LIMIT = 1 << 20
 RT_MAX_FRAMES = 128
