@@ -643,6 +643,69 @@ int rt_ao_rays_host(const rt_ray* points, long long n, const rt_ao_params* param
 int rt_trace_gather(rt_scene* scene, const rt_render_params* p, const rt_ray* d_points, long long n,
                     const rt_ao_params* fan, void* d_rgb, rt_stats* stats, void* stream);
 
+/* A camera's closest hits and surface points made on the device: the G-buffer of a
+ * frame -- depth, normal, mesh id, hit point per pixel -- and the point records rt_trace_ao and
+ * rt_trace_gather start from, without a ray or a hit written out in between.  rt_trace_camera
+ * builds each pixel's primary ray in registers, finds its closest hit as rt_trace_closest does and
+ * stores, per pixel, the rt_hit, the surface-point record, or both; it reads nothing per pixel.
+ *   The ray of pixel (x, y) (csrc/device/rt_camera_point.hpp is the definition; fp64, + - * / sqrt
+ * only, no contraction, so host and device agree bit for bit):
+ *     o = eye,  d = ((lower_left + x * x_dir) + y * y_dir) - eye       (per component, unnormalised)
+ * with tmax = +inf and reserved_ = 0: the render kernel's primary ray at spp_n = 1.
+ *   The surface point of a ray and its rt_hit; the hit counts iff hit.t < +inf:
+ *     rd = d / sqrt(dot(d, d))                                          (the renderer's normalize)
+ *     p = o + hit.t * rd,  n = hit.normal, negated if n.x * d.x + n.y * d.y + n.z * d.z > 0
+ * (the normal faces the ray's origin), and the record is {o = p, d = n, tmax = point_tmax,
+ * reserved_ = 0}.  A miss gives {o = the ray's o, d = (0, 0, 0), tmax = point_tmax, reserved_ = 0}: a
+ * degenerate point, which rt_trace_ao reports as fully open and rt_trace_gather as background.
+ *   Read from p: camera, row_begin, row_end, stripe_height, stripe_count, stripe_index.  The shard's
+ * rows are rt_launch_compute_image's, packed in increasing y (rt_rows_in_shard(p) of them); n = rows
+ * x width records.  Lights, depth, colours and out_format are ignored.
+ *   Order of the records: RT_CAMERA_ROW_MAJOR puts pixel (x, local row r) at record r * width + x,
+ * the frame's own layout.  RT_CAMERA_TILE_MAJOR walks the tiles of rt_tile_shape (8 x 8) over the
+ * shard's packed rows, tile rows from the bottom, tiles left to right, a tile's pixels row-major
+ * and consecutive; the partial tiles at the right and top edges hold only the pixels they have, so
+ * there are still exactly n records and no padding.  Tile order is the coherent order for whatever
+ * traces from these points next.
+ *   The definition is compositional: with rays = rt_camera_rays_host(p, order), d_hits equals
+ * rt_trace_closest(rays) bit for bit (analytic primitives of rt_scene_set_analytic included) and
+ * d_points equals rt_surface_points_host(rays, those hits, n, point_tmax) bit for bit. */
+enum { RT_CAMERA_ROW_MAJOR = 0, RT_CAMERA_TILE_MAJOR = 1 };
+#define RT_CAMERA_MAX_PIXELS (1LL << 31)
+typedef struct rt_camera_out {
+  rt_hit* d_hits;      /* DEVICE, optional: the closest hit per pixel */
+  rt_ray* d_points;    /* DEVICE, optional: the surface-point record per pixel (rt_trace_ao / rt_trace_gather input) */
+  int order;           /* RT_CAMERA_* */
+  int reserved_;
+  double point_tmax;   /* tmax written into every point record (+inf: unbounded fans) */
+} rt_camera_out;
+
+/* Fills out->d_hits and / or out->d_points (n records each, device buffers) on `stream`.  It takes
+ * one of the scene's query contexts, as rt_trace_ao does -- it is not a render launch -- so it may be
+ * in flight beside renders and queries on other streams; it allocates nothing beyond the contexts'
+ * first-use allocation and touches no scene or cost-order state.  Asynchronous unless stats != NULL
+ * (then it synchronises the stream): rays = n, hits = the pixels that hit, stack_spills and
+ * watchdog as for the queries.
+ *   RT_ERR_INVALID, before any HIP call, for: a NULL scene, p or out; both output pointers NULL; an
+ * unknown order; spp_n != 1; any flag but RT_FLAG_NATURAL_ORDER, which is accepted and changes
+ * nothing; whatever rt_launch_compute_image rejects about the camera size, the row range and the
+ * stripes (a row range combined with stripe_count > 1 included); n > RT_CAMERA_MAX_PIXELS; d_points
+ * != NULL with point_tmax > 1e-5 false (NaN included).  RT_ERR_HIP on a scene whose watchdog word is
+ * set (rt_scene_status). */
+int rt_trace_camera(rt_scene* scene, const rt_render_params* p, const rt_camera_out* out, rt_query_stats* stats,
+                    void* stream);
+
+/* Pure host, no HIP call, no scene: rays_out[0..n) = the shard's primary rays in `order` (a HOST
+ * pointer), the same function text the device runs and the same checks of p and order. */
+int rt_camera_rays_host(const rt_render_params* p, int order, rt_ray* rays_out);
+
+/* Pure host, no HIP call, no scene: points_out[i] = the surface-point record of rays[i] and hits[i]
+ * (HOST pointers), i in [0, n), the same function text the device runs.  n == 0 is accepted;
+ * RT_ERR_INVALID for n < 0, n > RT_CAMERA_MAX_PIXELS, point_tmax > 1e-5 false, and a NULL buffer
+ * with n > 0. */
+int rt_surface_points_host(const rt_ray* rays, const rt_hit* hits, long long n, double point_tmax,
+                           rt_ray* points_out);
+
 /* Cross-process access to a device buffer, for one process per GPU (the frame-assembly mode
  * RT_FLAG_GLOBAL_ROWS: every rank writes its stripes straight into rank 0's frame buffer).
  * rt_ipc_get_handle exports the device allocation that holds d_ptr (an RT_IPC_HANDLE_BYTES-byte

@@ -3551,6 +3551,8 @@ struct StreamScratch {
 #include "rt_order.inc"
 // occlusion fans generated on the device: rt_trace_ao, rt_ao_rays_host
 #include "rt_ao.inc"
+// a camera's closest hits and surface points made on the device: rt_trace_camera
+#include "rt_camera.inc"
 
 namespace {
 // what a ray-list launch (rt_trace_radiance, rt_trace_gather) rejects about its render parameters,

@@ -672,6 +672,79 @@ class DeviceScene:
             out = out.cpu().numpy()
         return (out, st) if stats else out
 
+    def camera(self, params, hits=True, points=False, order="row", point_tmax=float("inf"), stats=False,
+               stream=None):
+        """A camera's closest hits and surface points made on the device (rt_trace_camera): per pixel
+        of params' shard (camera, row range, stripes; spp_n = 1) the closest hit of its primary ray
+        and / or the point record ao() and gather() start from, with no ray written out.  Returns a
+        dict: "hits" = the views trace() returns over one [n, 8] float64 tensor of rt_hit rows,
+        "points" = an [n, 8] float64 tensor (p xyz, the normal facing the eye, point_tmax, 0; a miss
+        is a degenerate point: p = eye, zero normal), n = rows_in_shard(params) * width; both stay on
+        the device.  order: "row" = the frame's layout (pixel (x, local row r) at r * W + x), "tile" =
+        the records of tile_major(W, rows), the coherent order for ao() / gather().  The values equal
+        trace(camera_rays_host(params, order)) and surface_points_host of them bit for bit.
+        Asynchronous on `stream` (an int pointer, None = the null stream) unless stats=True, which
+        returns (dict, QueryStats): rays = n, hits = the pixels that hit."""
+        import torch
+
+        fn = _camera_fn("rt_trace_camera")
+        if order not in _CAMERA_ORDERS:
+            raise ValueError(f"order must be one of {sorted(_CAMERA_ORDERS)}")
+        if not (hits or points):
+            raise ValueError("nothing requested: hits and points are both False")
+        dev = torch.device(f"cuda:{self.device}")
+        n = rows_in_shard(params) * params.camera.width
+        if not 0 <= n <= abi.RT_CAMERA_MAX_PIXELS:
+            raise ValueError("the shard holds more than RT_CAMERA_MAX_PIXELS pixels")
+        ht = torch.zeros((n, 8), dtype=torch.float64, device=dev) if hits else None
+        pt = torch.zeros((n, 8), dtype=torch.float64, device=dev) if points else None
+        out = abi.CameraOut(d_hits=ht.data_ptr() if hits else None, d_points=pt.data_ptr() if points else None,
+                            order=_CAMERA_ORDERS[order], point_tmax=float(point_tmax))
+        st = abi.QueryStats() if stats else None
+        if stream:   # the buffers above were made on torch's current stream
+            torch.cuda.current_stream(dev).synchronize()
+        if n:   # (an empty row range: nothing to trace, and torch gives empty tensors no address)
+            _check_hip(fn(self._h, C.byref(params), C.byref(out), C.byref(st) if st is not None else None,
+                          C.c_void_p(stream) if stream else None), "rt_trace_camera")
+        res = {}
+        if hits:
+            res["hits"] = _hit_views(ht)
+        if points:
+            res["points"] = pt
+        return (res, st) if stats else res
+
+    def _fan_image(self, params, radius, trace):
+        """ao_image / gather_image: tile-major surface points -> trace(points) -> image order."""
+        import torch
+
+        rows, W = rows_in_shard(params), params.camera.width
+        pts = self.camera(params, hits=False, points=True, order="tile", point_tmax=radius)["points"]
+        vals = trace(pts)
+        perm = torch.from_numpy(tile_major(W, rows)).to(vals.device)
+        img = torch.zeros_like(vals)
+        img[perm] = vals   # record j is pixel perm[j] of the row-major shard
+        return img
+
+    def ao_image(self, params, dirs, seed=0, bias=0.0, radius=float("inf")):
+        """Ambient occlusion of a camera's view, on the device end to end: [rows, W] float64 tensor,
+        the unoccluded fraction count / k of each pixel's fan in image order (row 0 at the bottom).
+        The composition camera(points, order="tile", point_tmax=radius) -> ao(points, dirs, seed,
+        bias) -> the values scattered back with tile_major(W, rows); a pixel that sees the
+        background reports 1.  params as for camera(), dirs as for ao()."""
+        import torch
+
+        k = dirs.shape[1]
+        img = self._fan_image(params, radius, lambda pts: self.ao(pts, dirs, seed=seed, bias=bias))
+        return (img.to(torch.float64) / float(k)).reshape(rows_in_shard(params), params.camera.width)
+
+    def gather_image(self, params, dirs, seed=0, bias=0.0):
+        """Mean fan radiance of a camera's view: [rows, W, 3] tensor in params.out_format's dtype, the
+        colour gather() returns for each pixel's surface point, in image order.  The composition
+        camera(points, order="tile") -> gather(points, dirs, params, seed, bias) -> the colours
+        scattered back with tile_major(W, rows); a pixel that sees the background reports it."""
+        img = self._fan_image(params, float("inf"), lambda pts: self.gather(pts, dirs, params, seed=seed, bias=bias))
+        return img.reshape(rows_in_shard(params), params.camera.width, 3)
+
     def debug_counters(self):
         """Raw counter words of the last launch (see rt_debug_counters in rt_hip.h)."""
         buf = (C.c_ulonglong * 40)()
@@ -860,6 +933,55 @@ def ao_points_from_hits(rays, hits):
     pts[:, 0:3] = torch.where(hit[:, None], p, rays[:, 0:3])
     pts[:, 3:6] = torch.where(hit[:, None], nrm, torch.zeros_like(nrm))
     pts[:, 6] = float("inf")
+    return pts
+
+
+_CAMERA_ORDERS = {"row": abi.RT_CAMERA_ROW_MAJOR, "tile": abi.RT_CAMERA_TILE_MAJOR}
+
+
+def _camera_fn(name):
+    """An entry point of the camera feature (a partial RTAMD_HIP_LIB, built from an older source,
+    may lack it)."""
+    try:
+        return getattr(hip_lib(), name)
+    except AttributeError:
+        raise RtError(f"{name}: not exported by this librt_hip.so (RTAMD_HIP_LIB)") from None
+
+
+def camera_rays_host(params, order="row"):
+    """The primary rays DeviceScene.camera traces, written out on the CPU by the function the device
+    runs (rt_camera_rays_host): [n, 8] float64 rays (o = eye, d unnormalised, tmax = inf, 0) of
+    params' shard -- its row range or stripes -- n = rows_in_shard(params) * width, in order "row"
+    (pixel (x, local row r) at r * W + x) or "tile" (the records of tile_major(W, rows))."""
+    fn = _camera_fn("rt_camera_rays_host")
+    if order not in _CAMERA_ORDERS:
+        raise ValueError(f"order must be one of {sorted(_CAMERA_ORDERS)}")
+    n = rows_in_shard(params) * params.camera.width
+    if not 0 <= n <= abi.RT_CAMERA_MAX_PIXELS:
+        raise ValueError("the shard holds more than RT_CAMERA_MAX_PIXELS pixels")
+    rays = np.zeros((n, 8), dtype=np.float64)
+    _check_hip(fn(C.byref(params), _CAMERA_ORDERS[order], rays.ctypes.data_as(C.c_void_p) if n else None),
+               "rt_camera_rays_host")
+    return rays
+
+
+def surface_points_host(rays, hits_rows, point_tmax=float("inf")):
+    """The point records DeviceScene.camera writes, made on the CPU by the function the device runs
+    (rt_surface_points_host): rays [n, 8] float64 and hits_rows [n, 8] float64 rt_hit rows (the
+    buffer behind trace()'s views; only t and the normal are read) -> [n, 8] float64 point records
+    (p = o + t * normalize(d), the normal facing the ray's origin, point_tmax, 0); a miss (t = inf)
+    gives the degenerate point (o, zero normal)."""
+    fn = _camera_fn("rt_surface_points_host")
+    rays = np.ascontiguousarray(rays, dtype=np.float64)
+    hits_rows = np.ascontiguousarray(hits_rows, dtype=np.float64)
+    if rays.ndim != 2 or rays.shape[1] != 8:
+        raise ValueError("rays must be an [n, 8] float64 array")
+    if hits_rows.shape != rays.shape:
+        raise ValueError("hits_rows must be an [n, 8] float64 array of rt_hit rows, one per ray")
+    n = len(rays)
+    pts = np.zeros((n, 8), dtype=np.float64)
+    _check_hip(fn(rays.ctypes.data_as(C.c_void_p) if n else None, hits_rows.ctypes.data_as(C.c_void_p) if n else None,
+                  n, float(point_tmax), pts.ctypes.data_as(C.c_void_p) if n else None), "rt_surface_points_host")
     return pts
 
 

@@ -34,6 +34,9 @@ RT_ORDER_TILE = 1024
 RT_AO_MAX_SAMPLES = 1024
 RT_AO_MAX_SETS = 65536
 RT_AO_MAX_POINTS = 1 << 31
+RT_CAMERA_ROW_MAJOR = 0
+RT_CAMERA_TILE_MAJOR = 1
+RT_CAMERA_MAX_PIXELS = 1 << 31
 RT_MULTI_GATHER = 0
 RT_MULTI_PEER = 1
 RT_MULTI_DEBUG_PEER_MISMATCH = 1
@@ -169,6 +172,12 @@ class AoParams(C.Structure):
                 ("bias", C.c_double), ("d_dirs", C.c_void_p)]
 
 
+class CameraOut(C.Structure):
+    """rt_camera_out: what rt_trace_camera writes (device pointers, either may be None) and how."""
+    _fields_ = [("d_hits", C.c_void_p), ("d_points", C.c_void_p), ("order", C.c_int), ("reserved_", C.c_int),
+                ("point_tmax", C.c_double)]
+
+
 class GenParams(C.Structure):
     _fields_ = [("width", C.c_int), ("height", C.c_int), ("n_triangles", C.c_longlong),
                 ("seed", C.c_ulonglong), ("max_depth", C.c_int), ("detail", C.c_int)]
@@ -251,6 +260,10 @@ HIP_SYMBOLS = {
     "rt_ao_rays_host": (C.c_int, [C.c_void_p, C.c_longlong, C.POINTER(AoParams), C.c_void_p]),
     "rt_trace_gather": (C.c_int, [C.c_void_p, C.POINTER(RenderParams), C.c_void_p, C.c_longlong, C.POINTER(AoParams),
                                   C.c_void_p, C.POINTER(Stats), C.c_void_p]),
+    "rt_trace_camera": (C.c_int, [C.c_void_p, C.POINTER(RenderParams), C.POINTER(CameraOut), C.POINTER(QueryStats),
+                                  C.c_void_p]),
+    "rt_camera_rays_host": (C.c_int, [C.POINTER(RenderParams), C.c_int, C.c_void_p]),
+    "rt_surface_points_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_double, C.c_void_p]),
     "rt_last_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "rt_tile_shape": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "rt_ipc_get_handle": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_ulonglong)]),
