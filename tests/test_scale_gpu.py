@@ -5,7 +5,8 @@ that these inputs are free of the reference's measure-zero divergences and not v
 The 4-wide production kernels evaluate a box slab as one fused plane * inv - o * inv, which the
 oracle does not model: it stays conservative only because the origin is first moved to the root
 box's entry point in fp64 and the box growth delta = 2^-20 max|vertex| is relative.
-That set-up exists three times (rt_render.hip, rt_query.inc, rt_ao.inc); every copy is reached here.
+That set-up exists twice (rt_render.hip, and rt_walk_body.inc, which the query, AO and camera kernels
+include); both texts, and every kernel that holds one, are reached here.
 
 Tolerances are those of tests/test_gpu_parity.py: fp64 output within 1e-12, fp32 output within 1e-6,
 ray counts exact; query results bit for bit (query_cases.check_hits)."""
