@@ -706,6 +706,67 @@ int rt_camera_rays_host(const rt_render_params* p, int order, rt_ray* rays_out);
 int rt_surface_points_host(const rt_ray* rays, const rt_hit* hits, long long n, double point_tmax,
                            rt_ray* points_out);
 
+/* Moving geometry: new vertex positions and normals on the uploaded topology, the
+ * device hierarchy refitted on the GPU -- a door that opens, a character that walks, a mesh that
+ * deforms -- without rt_scene_free + rt_scene_upload_ex and their host build.  The three arrays are
+ * those of the rt_scene_soa the scene was uploaded from, with new values: rt_host_update_vertices
+ * (rt_host.h) makes them.
+ *   The definition is compositional: after the call every launch and query on the scene returns,
+ * bit for bit, what it returns on a scene freshly uploaded with the same options from the original
+ * rt_scene_soa with these three arrays replaced and the same reference tree with refitted boxes
+ * (frames, adaptive passes, rt_trace_closest / occluded / radiance / ao / gather / camera, the ray
+ * counts of rt_stats).  Indices, uvs, texels, materials, analytic primitives and the slot numbering
+ * are unchanged.  The device hierarchy keeps its topology and gets new boxes: a leaf slot the exact
+ * bounds of its whole triangles (under RT_TREE_SBVH larger than the clipped pieces of the upload,
+ * but conservative), an internal slot the union of its child node's slots, all grown by the new
+ * delta = 2^-20 max|vertex| and rounded outward as at upload.  No child reference is written.
+ *   Which tree to upload a scene that will move with (measured): RT_TREE_SAH.  Its
+ * refitted boxes render as fast as a fresh RT_TREE_SAH upload of the moved scene.  The un-clipped
+ * leaves of the default RT_TREE_SBVH cost the office proxy a factor of 29 to 39 per frame at every
+ * displacement, 1.4 in a room with few spatial splits; results are correct either way. */
+typedef struct rt_scene_update {
+  long long n_vertices;          /* must equal the uploaded scene's */
+  long long n_triangles;         /* must equal the uploaded scene's */
+  const double* vertex_pos;      /* HOST [3*n_vertices] */
+  const double* vertex_normals;  /* HOST [3*n_vertices] */
+  const double* face_normals;    /* HOST [3*n_triangles], leaf order of the uploaded rt_scene_soa */
+  long long reserved_[3];
+} rt_scene_update;
+
+/* Host part, synchronous and before any HIP call: RT_ERR_INVALID for a NULL scene, u or array, or a
+ * count that differs from the scene's; RT_ERR_UNSUPPORTED for max|vertex| above RT_MAX_COORDINATE
+ * (rt_scene_upload's rule; NaN coordinates are not looked for, their triangles enter no box and are
+ * never hit), the scene left exactly as it was; RT_ERR_HIP on a scene whose watchdog word is set.  A
+ * scene without triangles returns RT_OK without a launch.  The scene's delta and root box switch at
+ * the call: launches copy them by value, so a launch issued after the call returns sees the new
+ * ones, and rt_scene_bounds and the keys of rt_ray_order follow the new box (the bounds of the
+ * vertices the triangles reference, grown by delta).
+ *   Device part, asynchronous, on the stream a render launch given this `stream` would use
+ * (rt_upload_options.reserve_cus: the caller's CU-masked stream, joined to `stream` by events): the
+ * three arrays are copied -- the host arrays may be reused when the call returns --, one kernel
+ * rewrites the triangle and normal records, and one kernel per height of the 4-wide tree refits
+ * the boxes, leaf-only nodes first.  Stream order orders the update against launches on the same
+ * stream.  Launches issued earlier on OTHER streams must have finished before the call: the caller
+ * ensures it, it is not checked.  Calls on one scene must come from one host thread at a time.
+ *   The scene's first call allocates device copies of the three arrays and the refit schedule (it
+ * reads the node references and the records' vertex ids back once): rt_scene_device_bytes grows
+ * then and only then.  A scene that is never updated costs what it did before this call existed.
+ *   Not built: RT_FLAG_TRAVERSAL_STATS on a scene that has been updated returns RT_ERR_UNSUPPORTED
+ * (the canonical counters are the oracle's walk of the median-split tree of the current geometry;
+ * a refitted tree is another tree, so the 2-wide nodes are not refitted; RT_FLAG_WIDE_STATS keeps
+ * working); topology changes (triangles added or removed); a rebuild when the refitted boxes'
+ * quality decays; an rt_multi wrapper (each rt_scene of rt_scene_upload_multi can be updated on its
+ * own). */
+int rt_scene_update_vertices(rt_scene* scene, const rt_scene_update* u, void* stream);
+
+/* Test hook in the style of rt_debug_counters: copies a device array of the scene's layout into
+ * out[0 .. min(bytes, size)) -- RT_IMAGE_NODES4: the 4-wide nodes (128 B each: lo / hi of x, y, z
+ * for 4 slots as fp32, 4 refs, 4 pad words), RT_IMAGE_TRIS: the triangle records (80 B each),
+ * RT_IMAGE_TNORM: the normal records (12 doubles each) -- and returns the bytes the array holds
+ * (out may be NULL with bytes = 0 to ask for it).  Synchronises the device. */
+enum { RT_IMAGE_NODES4 = 0, RT_IMAGE_TRIS = 1, RT_IMAGE_TNORM = 2 };
+long long rt_debug_scene_image(rt_scene* scene, int what, void* out, long long bytes);
+
 /* Cross-process access to a device buffer, for one process per GPU (the frame-assembly mode
  * RT_FLAG_GLOBAL_ROWS: every rank writes its stripes straight into rank 0's frame buffer).
  * rt_ipc_get_handle exports the device allocation that holds d_ptr (an RT_IPC_HANDLE_BYTES-byte

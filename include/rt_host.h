@@ -54,6 +54,19 @@ int rt_host_prepare(rt_host_scene* s, double* seconds);
  * The tree and the slot permutation do not depend on it.  The library reads no environment. */
 int rt_host_prepare_ex(rt_host_scene* s, int build_threads, double* seconds);
 
+/* Moves the vertices of a prepared scene and keeps its topology: vertex_pos holds 3 * n_vertices
+ * doubles in global vertex order (the order of rt_scene_soa.vertex_pos).  Every mesh's positions are
+ * replaced, in the raw scene too (rt_host_raw sees the moved scene); face and vertex normals are
+ * recomputed as rt_host_prepare computes them; vertex_pos, vertex_normals and face_normals of the
+ * SoA are rewritten, face normals in the existing leaf order; bb_min / bb_max of the reference tree
+ * are refitted bottom-up (a leaf: the exact min / max of its triangles' vertices, an internal node:
+ * the min / max of its two children).  vertex_idx, texture_idx, left_child, first_tri, tri_count
+ * and n_nodes stay untouched, so the slots are the ones before the call and the pointers of
+ * rt_host_soa / rt_host_bvh stay valid.  The pair feeds rt_scene_update_vertices (rt_hip.h) and a
+ * fresh rt_scene_upload alike.  RT_ERR_INVALID for a scene that is not prepared, a NULL pointer or
+ * an n_vertices other than the scene's. */
+int rt_host_update_vertices(rt_host_scene* s, const double* vertex_pos, long long n_vertices);
+
 /* Valid after rt_host_prepare. */
 const rt_scene_soa* rt_host_soa(const rt_host_scene* s);
 const rt_bvh_soa* rt_host_bvh(const rt_host_scene* s);

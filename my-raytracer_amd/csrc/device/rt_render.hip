@@ -68,6 +68,7 @@
 #pragma clang fp contract(off)
 
 #include "rt_ao_fan.hpp"   // the fan of a surface point (gather_kernel below, rt_ao.inc)
+#include "rt_refit.hpp"    // records and boxes of moved vertices (rt_update.inc)
 
 using namespace rtk;
 
@@ -2740,6 +2741,7 @@ struct LaunchCtx {
 };
 
 struct QueryRing;   // ray-query contexts (rt_query.inc)
+struct UpdateState; // device arrays and refit schedule of rt_scene_update_vertices (rt_update.inc)
 
 struct rt_scene {
   int device = 0;
@@ -2817,6 +2819,10 @@ struct rt_scene {
   int n_masked = 0;
   QueryRing* query = nullptr;   // allocated by the scene's first ray query (rt_trace_closest / rt_trace_occluded)
   int order_grid = 0;           // rt_debug_set_order_grid: block cap of rt_ray_order's sort (0: from n_cu)
+  long long n_vertices = 0;     // of the uploaded rt_scene_soa
+  long long n_rec = 0;          // device records (d_tris, d_shade, d_tnorm)
+  UpdateState* update = nullptr;   // allocated by the scene's first rt_scene_update_vertices
+  bool updated = false;         // the vertices were moved: d_nodes (the canonical 2-wide tree) is stale
 };
 
 namespace {
@@ -2883,6 +2889,8 @@ int upload_image(const SceneImage& I, const rt_upload_options& opt, int device, 
   }
   sc->n_gnodes = (int)I.nodes.size();
   sc->n_tris = I.n_tris;
+  sc->n_vertices = I.n_vertices;
+  sc->n_rec = (long long)I.tris.size();
   sc->n_meshes = I.n_meshes;
   sc->mesh_mats = I.mats;
   sc->table_bytes = (long long)(std::max<size_t>(I.mats.size(), 1) * sizeof(GMat));
@@ -3216,6 +3224,8 @@ int launch_render(rt_scene* sc, const rt_render_params* p, int n_frames, void* c
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   HIP_TRY(hipSetDevice(sc->device));
   if (guard_tripped(sc)) return fail(RT_ERR_HIP, kGuardMsg);
+  if ((p->flags & RT_FLAG_TRAVERSAL_STATS) && sc->updated)   // the 2-wide nodes are not refitted
+    return fail(RT_ERR_UNSUPPORTED, "RT_FLAG_TRAVERSAL_STATS is not supported after rt_scene_update_vertices");
 
   KParams P;
   std::memset(&P, 0, sizeof P);
@@ -3553,6 +3563,8 @@ struct StreamScratch {
 #include "rt_ao.inc"
 // a camera's closest hits and surface points made on the device: rt_trace_camera
 #include "rt_camera.inc"
+// moving the scene's vertices, boxes refitted on the device: rt_scene_update_vertices
+#include "rt_update.inc"
 
 namespace {
 // what a ray-list launch (rt_trace_radiance, rt_trace_gather) rejects about its render parameters,
@@ -4139,6 +4151,7 @@ void rt_scene_free(rt_scene* sc) {
     if (q) (void)hipFree(q);
   if (sc->h_guard) (void)hipHostFree(sc->h_guard);
   query_ring_free(sc);
+  update_state_free(sc);
   for (LaunchCtx& c : sc->ctx) {
     void* cp[] = {c.d_ctr, c.d_pstate, c.d_spill, c.d_wavelog, c.d_tl, c.d_wctr};
     for (void* q : cp)

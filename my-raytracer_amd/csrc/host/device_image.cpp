@@ -12,6 +12,7 @@
 //     (outward rounding + delta growth), fp64 triangle / shading records in device order.
 // Parallel builds partition work so the result never depends on the thread count (tested).
 #include "device_image.hpp"
+#include "../device/rt_refit.hpp"
 
 #include <algorithm>
 #include <array>
@@ -40,16 +41,9 @@ int fail(int code, const std::string& msg) {
   return code;
 }
 
-float round_down_host(double x) {
-  float f = (float)x;
-  if ((double)f > x) f = std::nextafterf(f, -INFINITY);
-  return f;
-}
-float round_up_host(double x) {
-  float f = (float)x;
-  if ((double)f < x) f = std::nextafterf(f, INFINITY);
-  return f;
-}
+// outward fp32 rounding of a box bound: the text the device's refit runs (rt_refit.hpp)
+float round_down_host(double x) { return rt_refit_round_down(x); }
+float round_up_host(double x) { return rt_refit_round_up(x); }
 
 #ifndef RT_LEAF_MAX
 #define RT_LEAF_MAX 1
@@ -1523,11 +1517,7 @@ int build_image(const rt_scene_soa* s, const rt_bvh_soa* b, const rt_upload_opti
     const double* p1 = s->vertex_pos + 3 * (size_t)v1;
     const double* p2 = s->vertex_pos + 3 * (size_t)v2;
     GTri& T = tris[g];
-    for (int k = 0; k < 3; ++k) {
-      T.e1[k] = p0[k] - p2[k];
-      T.e2[k] = p1[k] - p2[k];
-      T.p2[k] = p2[k];
-    }
+    rt_refit_record(p0, p1, p2, T.e1, T.e2, T.p2);
     T.mesh = s->vertex_mesh_id[v0];                 // meshId = vertexMeshId_[vi0], mytracer_gpu.cu:492
     T.meta = (uint32_t)i | (last[i] ? kLastRef : 0u) | (last_dev[g] ? kLastDev : 0u);
     TriShade& sh = shade[g];
@@ -1585,6 +1575,7 @@ int build_image(const rt_scene_soa* s, const rt_bvh_soa* b, const rt_upload_opti
   I.tnorm = std::move(tnorm);
   I.mats = std::move(mats);
   I.n_tris = nt;
+  I.n_vertices = s->n_vertices;
   I.n_meshes = s->n_meshes;
   I.depth = depth;
   I.stack4 = stack4;

@@ -30,6 +30,7 @@ struct SceneImage {
   std::vector<unsigned char> texels;
   std::vector<GMat> mats;
   long long n_tris = 0;
+  long long n_vertices = 0;
   int n_meshes = 0;
   int depth = 0, stack4 = 1;
   double delta = 0.0;

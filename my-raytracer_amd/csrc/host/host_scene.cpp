@@ -149,6 +149,8 @@ void build_data(const HostScene& scene, SoA& s) {
   s.face_normals.resize(3 * nt);
   s.vertex_idx.resize(3 * nt);
   s.texture_idx.resize(3 * nt);
+  s.slot_tri.resize(nt);
+  for (long long t = 0; t < nt; ++t) s.slot_tri[t] = (int)t;
   s.tex_u.resize(nuv);
   s.tex_v.resize(nuv);
   s.texels.resize(3 * ntex);
@@ -274,6 +276,7 @@ void build_subtree(BuildCtx& cx, std::vector<FragNode>& arena, int root) {
           std::swap(s.texture_idx[3 * (size_t)i + k], s.texture_idx[3 * (size_t)j + k]);
           std::swap(cx.cent[3 * (size_t)i + k], cx.cent[3 * (size_t)j + k]);
         }
+        std::swap(s.slot_tri[i], s.slot_tri[j]);
         --j;
       }
     }
@@ -467,6 +470,45 @@ void HostScene::prepare(int threads) {
   prepared = true;
 }
 
+// rt_host_update_vertices: the prepared scene with its vertices moved.  Topology, slots and node
+// ids stay; normals come from the text prepare runs, the reference tree's boxes are refitted
+// bottom-up (children carry larger ids than their parent: they are numbered when it splits).
+bool HostScene::update_vertices(const double* pos, long long nv) {
+  if (!prepared || !pos || nv != soa.n_vertices) return false;
+  const long long nt = soa.n_vertex_idx / 3;
+  std::vector<double> fn(3 * (size_t)nt);   // face normals in build_Data's order
+  for (size_t mi = 0; mi < meshes.size(); ++mi) {
+    HostMesh& m = meshes[mi];
+    const size_t vbase = (size_t)soa.first_vertex[mi];
+    std::copy(pos + 3 * vbase, pos + 3 * (vbase + (size_t)m.n_vertices()), m.positions.begin());
+    m.compute_normals();
+    std::copy(m.vertex_normals.begin(), m.vertex_normals.end(), soa.vertex_normals.begin() + 3 * vbase);
+    std::copy(m.face_normals.begin(), m.face_normals.end(), fn.begin() + (size_t)soa.first_vertex_idx[mi]);
+  }
+  std::copy(pos, pos + 3 * (size_t)nv, soa.vertex_pos.begin());
+  for (long long i = 0; i < nt; ++i)
+    for (int k = 0; k < 3; ++k) soa.face_normals[3 * (size_t)i + k] = fn[3 * (size_t)soa.slot_tri[i] + k];
+  for (int n = bvh.n_nodes - 1; n >= 0; --n) {
+    double* mn = &bvh.bb_min[3 * (size_t)n];
+    double* mx = &bvh.bb_max[3 * (size_t)n];
+    if (bvh.tri_count[n] > 0) {   // a leaf: the exact bounds of its triangles, as updateNodeBoundsSoA
+      FragNode nd;
+      nd.first = bvh.first_tri[n];
+      nd.count = bvh.tri_count[n];
+      node_bounds(soa, nd);
+      for (int k = 0; k < 3; ++k) { mn[k] = nd.mn[k]; mx[k] = nd.mx[k]; }
+    } else {
+      const size_t l = (size_t)bvh.left_child[n], r = l + 1;
+      for (int k = 0; k < 3; ++k) {
+        mn[k] = std::fmin(bvh.bb_min[3 * l + k], bvh.bb_min[3 * r + k]);
+        mx[k] = std::fmax(bvh.bb_max[3 * l + k], bvh.bb_max[3 * r + k]);
+      }
+    }
+  }
+  refresh_raw();
+  return true;
+}
+
 }  // namespace rt
 
 // ---------------------------------------------------------------------------
@@ -533,6 +575,15 @@ int rt_host_prepare_ex(rt_host_scene* s, int build_threads, double* seconds) {
   } catch (const std::exception& e) {
     return host_fail(std::string("rt_host_prepare: ") + e.what());
   }
+}
+
+int rt_host_update_vertices(rt_host_scene* s, const double* vertex_pos, long long n_vertices) {
+  if (!s || !vertex_pos) return host_fail("rt_host_update_vertices: null argument");
+  if (!s->scene.prepared) return host_fail("rt_host_update_vertices: scene not prepared");
+  if (n_vertices != s->scene.soa.n_vertices)
+    return host_fail("rt_host_update_vertices: n_vertices differs from the scene's");
+  if (!s->scene.update_vertices(vertex_pos, n_vertices)) return host_fail("rt_host_update_vertices: failed");
+  return RT_OK;
 }
 
 const rt_scene_soa* rt_host_soa(const rt_host_scene* s) {

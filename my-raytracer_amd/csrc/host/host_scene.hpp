@@ -42,6 +42,7 @@ struct SoA {
   std::vector<int> vertex_mesh_id;
   std::vector<double> vertex_pos, vertex_normals, face_normals;
   std::vector<int> vertex_idx, texture_idx;
+  std::vector<int> slot_tri;   // leaf slot -> triangle in build_Data's order (the permutation initSoA applied)
   std::vector<double> tex_u, tex_v;
   std::vector<unsigned char> texels;
   std::vector<int> first_vertex, vertex_count, first_vertex_idx, vertex_idx_count;
@@ -82,6 +83,8 @@ struct HostScene {
 
   void refresh_raw();              // rebuild the rt_raw_scene view
   void prepare(int build_threads = 0);   // compute_normals + build_Data + initSoA (0 threads: usable CPUs)
+  // rt_host_update_vertices: new positions (global vertex order) on the prepared topology; false = wrong count
+  bool update_vertices(const double* vertex_pos, long long n_vertices);
   long long triangle_count() const;
 };
 

@@ -183,6 +183,19 @@ class HostScene:
         _check_host(host_lib().rt_host_prepare_ex(self.handle, int(build_threads), C.byref(secs)), "prepare")
         return secs.value
 
+    def update_vertices(self, pos):
+        """rt_host_update_vertices: moves the prepared scene's vertices to pos ([n_vertices, 3] float64,
+        global vertex order, as soa_arrays()["vertex_pos"]) and keeps its topology: normals recomputed,
+        the SoA's vertex_pos / vertex_normals / face_normals rewritten in place (face normals in the
+        existing leaf order), the reference tree's boxes refitted; indices, slots and node ids stay.
+        raw and an Oracle made afterwards see the moved scene.  Feeds DeviceScene.update and a fresh
+        DeviceScene alike."""
+        pos = np.ascontiguousarray(pos, dtype=np.float64)
+        if pos.ndim != 2 or pos.shape[1] != 3:
+            raise ValueError("pos must be an [n_vertices, 3] float64 array")
+        _check_host(host_lib().rt_host_update_vertices(self.handle, pos.ctypes.data_as(C.POINTER(C.c_double)),
+                                                       len(pos)), "update_vertices")
+
     @property
     def raw(self):
         return host_lib().rt_host_raw(self.handle)
@@ -296,6 +309,57 @@ class DeviceScene:
         b, c = C.c_double(), C.c_double()
         _check_hip(hip_lib().rt_scene_upload_seconds(self._h, C.byref(b), C.byref(c)), "rt_scene_upload_seconds")
         return b.value, c.value
+
+    def update(self, host_scene, stream=None):
+        """rt_scene_update_vertices with the three arrays of a host scene's SoA: the HostScene this
+        scene was uploaded from after HostScene.update_vertices, or any prepared scene of the same
+        topology and slots."""
+        s = host_scene.soa.contents
+        u = abi.SceneUpdate(n_vertices=s.n_vertices, n_triangles=s.n_vertex_idx // 3, vertex_pos=s.vertex_pos,
+                            vertex_normals=s.vertex_normals, face_normals=s.face_normals)
+        _check_hip(_update_fn("rt_scene_update_vertices")(self._h, C.byref(u), C.c_void_p(stream) if stream else None),
+                   "rt_scene_update_vertices")
+
+    def update_vertices(self, vertex_pos, vertex_normals, face_normals, stream=None):
+        """Moves the scene's vertices on the device (rt_scene_update_vertices): new positions and
+        vertex normals ([n_vertices, 3] float64) and face normals ([n_triangles, 3] float64, leaf
+        order of the uploaded SoA) on the uploaded topology; the triangle and normal records are
+        rewritten and the 4-wide hierarchy's boxes refitted by kernels on `stream` (an int pointer,
+        None = the null stream).  Afterwards every launch and query returns what a fresh upload of
+        the moved scene returns, bit for bit.  The arrays may be reused when the call returns.
+        Upload a scene that will move with tree="sah": the default SBVH's clipped leaf boxes become
+        whole-triangle boxes at the first update (correct, but 29-39x slower frames on the office
+        proxy)."""
+        arrs = [np.ascontiguousarray(a, dtype=np.float64) for a in (vertex_pos, vertex_normals, face_normals)]
+        for a in arrs:
+            if a.ndim != 2 or a.shape[1] != 3:
+                raise ValueError("vertex_pos, vertex_normals and face_normals must be [n, 3] float64 arrays")
+        if len(arrs[0]) != len(arrs[1]):
+            raise ValueError("vertex_pos and vertex_normals differ in length")
+        dp = C.POINTER(C.c_double)
+        u = abi.SceneUpdate(n_vertices=len(arrs[0]), n_triangles=len(arrs[2]), vertex_pos=arrs[0].ctypes.data_as(dp),
+                            vertex_normals=arrs[1].ctypes.data_as(dp), face_normals=arrs[2].ctypes.data_as(dp))
+        _check_hip(_update_fn("rt_scene_update_vertices")(self._h, C.byref(u), C.c_void_p(stream) if stream else None),
+                   "rt_scene_update_vertices")
+
+    def debug_scene_image(self, what):
+        """Test hook (rt_debug_scene_image): the device's "nodes4" ([n, 32] uint32 view of the 128-B
+        nodes: lo / hi of x, y, z for 4 slots as fp32 bits, 4 refs, 4 pad words), "tris" ([n, 20]
+        uint32 view of the 80-B records) or "tnorm" ([n, 12] float64) as a host array.  Synchronises."""
+        kinds = {"nodes4": (abi.RT_IMAGE_NODES4, np.uint32, 32), "tris": (abi.RT_IMAGE_TRIS, np.uint32, 20),
+                 "tnorm": (abi.RT_IMAGE_TNORM, np.float64, 12)}
+        if what not in kinds:
+            raise ValueError(f"what must be one of {sorted(kinds)}")
+        code, dtype, width = kinds[what]
+        fn = _update_fn("rt_debug_scene_image")
+        size = int(fn(self._h, code, None, 0))
+        if size < 0:
+            _check_hip(size, "rt_debug_scene_image")
+        out = np.zeros(size // np.dtype(dtype).itemsize, dtype=dtype)
+        got = int(fn(self._h, code, out.ctypes.data_as(C.c_void_p), size))
+        if got < 0:
+            _check_hip(got, "rt_debug_scene_image")
+        return out.reshape(-1, width)
 
     def launch(self, params, d_out, stats=False, stream=None):
         """Asynchronous render into a device buffer (int pointer); returns Stats if stats=True."""
@@ -801,6 +865,15 @@ def _hit_views(out):
     ints = out.view(torch.int32)
     return {"t": out[:, 0], "alpha": out[:, 1], "beta": out[:, 2], "normal": out[:, 3:6],
             "slot": ints[:, 12], "mesh": ints[:, 13], "prim": ints[:, 14]}
+
+
+def _update_fn(name):
+    """An entry point of the vertex-update feature (a partial RTAMD_HIP_LIB, built from an older
+    source, may lack it)."""
+    try:
+        return getattr(hip_lib(), name)
+    except AttributeError:
+        raise RtError(f"{name}: not exported by this librt_hip.so (RTAMD_HIP_LIB)") from None
 
 
 def _order_fn(name):

@@ -178,6 +178,16 @@ class CameraOut(C.Structure):
                 ("point_tmax", C.c_double)]
 
 
+RT_IMAGE_NODES4, RT_IMAGE_TRIS, RT_IMAGE_TNORM = 0, 1, 2
+
+
+class SceneUpdate(C.Structure):
+    """rt_scene_update: the three HOST arrays of rt_scene_update_vertices."""
+    _fields_ = [("n_vertices", C.c_longlong), ("n_triangles", C.c_longlong), ("vertex_pos", C.POINTER(C.c_double)),
+                ("vertex_normals", C.POINTER(C.c_double)), ("face_normals", C.POINTER(C.c_double)),
+                ("reserved_", C.c_longlong * 3)]
+
+
 class GenParams(C.Structure):
     _fields_ = [("width", C.c_int), ("height", C.c_int), ("n_triangles", C.c_longlong),
                 ("seed", C.c_ulonglong), ("max_depth", C.c_int), ("detail", C.c_int)]
@@ -264,6 +274,8 @@ HIP_SYMBOLS = {
                                   C.c_void_p]),
     "rt_camera_rays_host": (C.c_int, [C.POINTER(RenderParams), C.c_int, C.c_void_p]),
     "rt_surface_points_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_double, C.c_void_p]),
+    "rt_scene_update_vertices": (C.c_int, [C.c_void_p, C.POINTER(SceneUpdate), C.c_void_p]),
+    "rt_debug_scene_image": (C.c_longlong, [C.c_void_p, C.c_int, C.c_void_p, C.c_longlong]),
     "rt_last_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "rt_tile_shape": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "rt_ipc_get_handle": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_ulonglong)]),
@@ -292,6 +304,7 @@ HOST_SYMBOLS = {
     "rt_host_raw": (C.POINTER(RawScene), [C.c_void_p]),
     "rt_host_prepare": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     "rt_host_prepare_ex": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double)]),
+    "rt_host_update_vertices": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_longlong]),
     "rt_host_soa": (C.POINTER(SceneSoA), [C.c_void_p]),
     "rt_host_bvh": (C.POINTER(BvhSoA), [C.c_void_p]),
     "rt_host_camera": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(Camera)]),
