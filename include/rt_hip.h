@@ -723,7 +723,13 @@ int rt_surface_points_host(const rt_ray* rays, const rt_hit* hits, long long n, 
  *   Which tree to upload a scene that will move with (measured): RT_TREE_SAH.  Its
  * refitted boxes render as fast as a fresh RT_TREE_SAH upload of the moved scene.  The un-clipped
  * leaves of the default RT_TREE_SBVH cost the office proxy a factor of 29 to 39 per frame at every
- * displacement, 1.4 in a room with few spatial splits; results are correct either way. */
+ * displacement, 1.4 in a room with few spatial splits; results are correct either way.
+ *   An RT_TREE_SBVH scene that is already uploaded, or one that moves little, keeps its clipped
+ * leaves with rt_scene_update_vertices_ex and RT_UPDATE_RECLIP below (measured, DESIGN.md §25: the
+ * office frame after the update within 1.03 of a fresh upload's at a displacement of 0.01 of the
+ * box diagonal and faster than the refitted RT_TREE_SAH tree's, 1.5 to 1.8 at 0.1 and 0.3, where at
+ * 0.1 the refitted RT_TREE_SAH tree is the faster of the two; a plain update of an RT_TREE_SBVH
+ * scene is never the better choice). */
 typedef struct rt_scene_update {
   long long n_vertices;          /* must equal the uploaded scene's */
   long long n_triangles;         /* must equal the uploaded scene's */
@@ -758,6 +764,39 @@ typedef struct rt_scene_update {
  * quality decays; an rt_multi wrapper (each rt_scene of rt_scene_upload_multi can be updated on its
  * own). */
 int rt_scene_update_vertices(rt_scene* scene, const rt_scene_update* u, void* stream);
+
+/* rt_scene_update_vertices with flags.  flags == 0 is that call exactly; a bit other
+ * than RT_UPDATE_RECLIP returns RT_ERR_INVALID before any HIP call.
+ *   RT_UPDATE_RECLIP keeps the clipped leaves of an RT_TREE_SBVH scene through the update.  The
+ * upload remembers, per device record, the region its spatial splits cut the record to (the regions of
+ * one triangle's records together cover all of space).  The refit bounds each cut record by the
+ * part of its moved triangle inside that region -- bounds(triangle), intersected per plane of the
+ * region with the bounds of the triangle's part on that side, in fp64 -- instead of by the whole
+ * triangle; a leaf slot whose triangles all left their regions gets the empty box [+inf, -inf],
+ * which no ray enters.  Everything else is rt_scene_update_vertices: the compositional definition
+ * above holds bit for bit, plain and re-clipping updates may alternate (every box is recomputed
+ * from the positions each time), RT_FLAG_TRAVERSAL_STATS stays refused.  The planes stay where the
+ * uploaded geometry put them: nothing is re-split.
+ *   On a scene without cut records (RT_TREE_SAH, RT_TREE_REFERENCE, an RT_TREE_SBVH build that
+ * duplicated no reference) the flag is accepted and the plain refit runs.  The scene's first
+ * re-clipping update copies the table to the device and rt_scene_device_bytes grows by
+ * 4 * records + 48 * cut records bytes, then and only then; a scene never re-clipped allocates
+ * nothing for it. */
+enum { RT_UPDATE_RECLIP = 1 };
+int rt_scene_update_vertices_ex(rt_scene* scene, const rt_scene_update* u, unsigned flags, void* stream);
+
+/* Pure host, no HIP call: the clip regions of the device records rt_scene_upload_ex builds from
+ * these arguments (opt NULL: the defaults).  Returns the record count, or an RT_ERR_* code; writes
+ * the first min(records, cap) rows: clip_out[6 * g ..] = lo xyz, hi xyz of record g (-inf / +inf where
+ * uncut), slot_out[g] = the reference slot of the record's triangle. */
+long long rt_debug_clip_regions(const rt_scene_soa* soa, const rt_bvh_soa* bvh, const rt_upload_options* opt,
+                                double* clip_out, int* slot_out, long long cap);
+
+/* Pure host: the fp64 box the re-clipping refit gives triangle (p0, p1, p2) in region clip (lo xyz,
+ * hi xyz), the function text the device runs.  1: non-empty, lo / hi written; 0: empty; RT_ERR_INVALID
+ * for a NULL pointer. */
+int rt_reclip_box_host(const double p0[3], const double p1[3], const double p2[3], const double clip[6],
+                       double lo[3], double hi[3]);
 
 /* Test hook in the style of rt_debug_counters: copies a device array of the scene's layout into
  * out[0 .. min(bytes, size)) -- RT_IMAGE_NODES4: the 4-wide nodes (128 B each: lo / hi of x, y, z

@@ -55,6 +55,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <thread>
 #include <vector>
@@ -69,6 +70,7 @@
 
 #include "rt_ao_fan.hpp"   // the fan of a surface point (gather_kernel below, rt_ao.inc)
 #include "rt_refit.hpp"    // records and boxes of moved vertices (rt_update.inc)
+#include "rt_reclip.hpp"   // ... and the box of a moved triangle in its record's clip region
 
 using namespace rtk;
 
@@ -2823,6 +2825,8 @@ struct rt_scene {
   long long n_rec = 0;          // device records (d_tris, d_shade, d_tnorm)
   UpdateState* update = nullptr;   // allocated by the scene's first rt_scene_update_vertices
   bool updated = false;         // the vertices were moved: d_nodes (the canonical 2-wide tree) is stale
+  std::shared_ptr<const ClipTable> clip;   // host: where the upload's spatial splits cut the records (null: nowhere);
+                                           // one copy among the scenes of rt_scene_upload_multi, released by rt_scene_free
 };
 
 namespace {
@@ -2891,6 +2895,7 @@ int upload_image(const SceneImage& I, const rt_upload_options& opt, int device, 
   sc->n_tris = I.n_tris;
   sc->n_vertices = I.n_vertices;
   sc->n_rec = (long long)I.tris.size();
+  sc->clip = I.clip;
   sc->n_meshes = I.n_meshes;
   sc->mesh_mats = I.mats;
   sc->table_bytes = (long long)(std::max<size_t>(I.mats.size(), 1) * sizeof(GMat));

@@ -1,5 +1,5 @@
-// rt_update.inc — moving a device scene's vertices: rt_scene_update_vertices, rt_debug_scene_image
-// (include/rt_hip.h; DESIGN.md §24).  Included by rt_render.hip.
+// rt_update.inc — moving a device scene's vertices: rt_scene_update_vertices(_ex), rt_debug_scene_image
+// (include/rt_hip.h; DESIGN.md §24, §25).  Included by rt_render.hip.
 //
 // The topology stays: vertex ids, slots, child references and the records' order are the upload's.
 // update_records_kernel rewrites every triangle record and its normals from the new arrays;
@@ -10,7 +10,7 @@
 //
 // The per-thread bodies are __host__ __device__ functions over plain pointers, so a stand-alone
 // host program can run the same text on a SceneImage (define RT_UPDATE_KERNELS_ONLY and include
-// rt_layout.hpp and rt_refit.hpp first).
+// rt_layout.hpp, rt_refit.hpp and rt_reclip.hpp first).
 
 namespace {
 
@@ -88,6 +88,51 @@ __host__ __device__ inline void refit_slot_body(uint32_t node, int slot, GNode4*
   N.loz[slot] = flo[2]; N.hiz[slot] = fhi[2];
 }
 
+// refit_slot_body with the leaf slots re-clipped (RT_UPDATE_RECLIP, DESIGN.md §25): a record whose
+// clip_idx is >= 0 grows the slot's fp64 box by rt_reclip_box of its moved triangle in region
+// clip_box[6 * clip_idx ..], by nothing where that is empty; an uncut record by its three vertices.
+// A leaf slot whose records all came out empty gets [+inf, -inf], the box of an absent child, which
+// every slab test misses, and keeps its ref.  Internal slots as in refit_slot_body.
+__host__ __device__ inline void reclip_slot_body(uint32_t node, int slot, GNode4* nodes4, uint32_t n_nodes,
+                                                 const GTri* tris, const TriShade* shade, long long n_rec,
+                                                 const double* vpos, double delta, const int32_t* clip_idx,
+                                                 const double* clip_box) {
+  GNode4& N = nodes4[node];
+  const uint32_t ref = N.ref[slot];
+  if (ref == kEmpty) return;
+  float flo[3], fhi[3];
+  if (ref & kLeaf) {
+    double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (long long g = (long long)(ref & ~kLeaf); g < n_rec; ++g) {
+      const TriShade sh = shade[g];
+      const int32_t row = clip_idx[g];
+      if (row < 0) {
+        for (int c = 0; c < 3; ++c) rt_refit_grow(lo, hi, vpos + 3 * (size_t)sh.v[c]);
+      } else {
+        double p[3][3], clip[6], blo[3], bhi[3];
+        for (int c = 0; c < 3; ++c)
+          for (int k = 0; k < 3; ++k) p[c][k] = vpos[3 * (size_t)sh.v[c] + k];
+        for (int k = 0; k < 6; ++k) clip[k] = clip_box[6 * (size_t)row + k];
+        if (rt_reclip_box(p[0], p[1], p[2], clip, blo, bhi)) {
+          rt_refit_grow(lo, hi, blo);
+          rt_refit_grow(lo, hi, bhi);
+        }
+      }
+      if (tris[g].meta & kLastDev) break;
+    }
+    rt_refit_leaf_box(lo, hi, delta, flo, fhi);   // (+inf - delta and -inf + delta stay: the empty box)
+  } else {
+    if (ref >= n_nodes) return;   // (no such reference in a layout build_image made)
+    const GNode4& Cn = nodes4[ref];
+    rt_refit_union4(Cn.lox, Cn.hix, &flo[0], &fhi[0]);
+    rt_refit_union4(Cn.loy, Cn.hiy, &flo[1], &fhi[1]);
+    rt_refit_union4(Cn.loz, Cn.hiz, &flo[2], &fhi[2]);
+  }
+  N.lox[slot] = flo[0]; N.hix[slot] = fhi[0];
+  N.loy[slot] = flo[1]; N.hiy[slot] = fhi[1];
+  N.loz[slot] = flo[2]; N.hiz[slot] = fhi[2];
+}
+
 #if defined(__HIPCC__)
 // one thread per device record
 __global__ void __launch_bounds__(kUpdBlock) update_records_kernel(GTri* tris, const TriShade* shade, double* tnorm,
@@ -106,6 +151,19 @@ __global__ void __launch_bounds__(kUpdBlock) refit_nodes4_kernel(GNode4* nodes4,
   if (i >= 4 * n_level) return;
   const uint32_t node = order[i >> 2];
   if (node < n_nodes) refit_slot_body(node, (int)(i & 3), nodes4, n_nodes, tris, shade, n_rec, vpos, delta);
+}
+
+// the same schedule with re-clipped leaf slots
+__global__ void __launch_bounds__(kUpdBlock) reclip_nodes4_kernel(GNode4* nodes4, uint32_t n_nodes, const uint32_t* order,
+                                                                  long long n_level, const GTri* tris,
+                                                                  const TriShade* shade, long long n_rec,
+                                                                  const double* vpos, double delta,
+                                                                  const int32_t* clip_idx, const double* clip_box) {
+  const long long i = (long long)blockIdx.x * kUpdBlock + threadIdx.x;
+  if (i >= 4 * n_level) return;
+  const uint32_t node = order[i >> 2];
+  if (node < n_nodes)
+    reclip_slot_body(node, (int)(i & 3), nodes4, n_nodes, tris, shade, n_rec, vpos, delta, clip_idx, clip_box);
 }
 #endif
 
@@ -149,6 +207,8 @@ struct UpdateState {
   double* d_vnorm = nullptr;    // [3 * n_vertices]
   double* d_fnorm = nullptr;    // [3 * n_tris], by slot
   uint32_t* d_order = nullptr;  // [n_gnodes4] node ids sorted by height
+  int32_t* d_clip_idx = nullptr;   // [n_rec], d_clip_box [6 * cut records]: the scene's clip table, copied by
+  double* d_clip_box = nullptr;    // its first RT_UPDATE_RECLIP update
   std::vector<long long> level_begin;
   std::vector<int> used_vertices;   // sorted, unique
   hipEvent_t ev_in = nullptr, ev_out = nullptr;   // reserve_cus: the caller's stream joined to the masked one
@@ -160,7 +220,7 @@ namespace {
 void update_state_free(rt_scene* sc) {
   UpdateState* U = sc->update;
   if (!U) return;
-  void* ptrs[] = {U->d_vpos, U->d_vnorm, U->d_fnorm, U->d_order};
+  void* ptrs[] = {U->d_vpos, U->d_vnorm, U->d_fnorm, U->d_order, U->d_clip_idx, U->d_clip_box};
   for (void* q : ptrs)
     if (q) (void)hipFree(q);
   if (U->ev_in) (void)hipEventDestroy(U->ev_in);
@@ -211,12 +271,47 @@ int update_state_init(rt_scene* sc) {
   return RT_OK;
 }
 
+// The first re-clipping update of a scene with a clip table: the table's device copy,
+// 4 * records + 48 * cut records bytes.  A failure leaves the scene as it was.
+int update_state_clip(rt_scene* sc) {
+  UpdateState& U = *sc->update;
+  if (U.d_clip_idx) return RT_OK;
+  const ClipTable& C = *sc->clip;
+  const size_t rows = C.box.size() / 6;
+  if ((long long)C.idx.size() != sc->n_rec || rows == 0)
+    return fail(RT_ERR_HIP, "rt_scene_update_vertices: the clip table does not match the device records");
+  for (const int32_t r : C.idx)
+    if (r < -1 || (r >= 0 && (size_t)r >= rows))
+      return fail(RT_ERR_HIP, "rt_scene_update_vertices: a clip index out of range");
+  const size_t ib = C.idx.size() * sizeof(int32_t), bb = C.box.size() * sizeof(double);
+  int32_t* d_idx = nullptr;
+  double* d_box = nullptr;
+  if (hipMalloc(reinterpret_cast<void**>(&d_idx), ib) != hipSuccess ||
+      hipMalloc(reinterpret_cast<void**>(&d_box), bb) != hipSuccess ||
+      hipMemcpy(d_idx, C.idx.data(), ib, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(d_box, C.box.data(), bb, hipMemcpyHostToDevice) != hipSuccess) {
+    if (d_idx) (void)hipFree(d_idx);
+    if (d_box) (void)hipFree(d_box);
+    return fail(RT_ERR_HIP, "rt_scene_update_vertices: copying the clip table failed");
+  }
+  U.d_clip_idx = d_idx;
+  U.d_clip_box = d_box;
+  U.bytes += (long long)(ib + bb);
+  sc->bytes += (long long)(ib + bb);
+  return RT_OK;
+}
+
 }  // namespace
 
 extern "C" {
 
 int rt_scene_update_vertices(rt_scene* sc, const rt_scene_update* u, void* stream) {
+  return rt_scene_update_vertices_ex(sc, u, 0u, stream);
+}
+
+int rt_scene_update_vertices_ex(rt_scene* sc, const rt_scene_update* u, unsigned flags, void* stream) {
   if (!sc || !u) return fail(RT_ERR_INVALID, "rt_scene_update_vertices: null argument");
+  if (flags & ~(unsigned)RT_UPDATE_RECLIP) return fail(RT_ERR_INVALID, "rt_scene_update_vertices: unknown flag");
   if (!u->vertex_pos || !u->vertex_normals || !u->face_normals)
     return fail(RT_ERR_INVALID, "rt_scene_update_vertices: null array");
   if (u->n_vertices != sc->n_vertices || u->n_triangles != sc->n_tris)
@@ -241,6 +336,12 @@ int rt_scene_update_vertices(rt_scene* sc, const rt_scene_update* u, void* strea
   const int irc = update_state_init(sc);
   if (irc != RT_OK) return irc;
   UpdateState& U = *sc->update;
+  // without a clip table (no record was cut) the re-clipping refit is the plain one
+  const bool reclip = (flags & RT_UPDATE_RECLIP) && sc->clip;
+  if (reclip) {
+    const int crc = update_state_clip(sc);
+    if (crc != RT_OK) return crc;
+  }
   // the root box: the referenced vertices' bounds, grown by delta (the reference root's box)
   double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
   for (const int v : U.used_vertices) rt_refit_grow(lo, hi, u->vertex_pos + 3 * (size_t)v);
@@ -268,9 +369,14 @@ int rt_scene_update_vertices(rt_scene* sc, const rt_scene_update* u, void* strea
   for (size_t h = 0; h + 1 < U.level_begin.size(); ++h) {   // leaf-only nodes first
     const long long n_level = U.level_begin[h + 1] - U.level_begin[h];
     if (n_level <= 0) continue;
-    hipLaunchKernelGGL(refit_nodes4_kernel, dim3((unsigned)((4 * n_level + kUpdBlock - 1) / kUpdBlock)), dim3(kUpdBlock),
-                       0, st, sc->d_nodes4, (uint32_t)sc->n_gnodes4, U.d_order + U.level_begin[h], n_level, sc->d_tris,
-                       sc->d_shade, n_rec, U.d_vpos, delta);
+    const dim3 grid((unsigned)((4 * n_level + kUpdBlock - 1) / kUpdBlock));
+    if (reclip)
+      hipLaunchKernelGGL(reclip_nodes4_kernel, grid, dim3(kUpdBlock), 0, st, sc->d_nodes4, (uint32_t)sc->n_gnodes4,
+                         U.d_order + U.level_begin[h], n_level, sc->d_tris, sc->d_shade, n_rec, U.d_vpos, delta,
+                         U.d_clip_idx, U.d_clip_box);
+    else
+      hipLaunchKernelGGL(refit_nodes4_kernel, grid, dim3(kUpdBlock), 0, st, sc->d_nodes4, (uint32_t)sc->n_gnodes4,
+                         U.d_order + U.level_begin[h], n_level, sc->d_tris, sc->d_shade, n_rec, U.d_vpos, delta);
     HIP_TRY(hipGetLastError());
   }
   if (st != caller) {   // the caller's later work follows the update

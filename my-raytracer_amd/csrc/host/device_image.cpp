@@ -13,6 +13,7 @@
 // Parallel builds partition work so the result never depends on the thread count (tested).
 #include "device_image.hpp"
 #include "../device/rt_refit.hpp"
+#include "../device/rt_reclip.hpp"
 
 #include <algorithm>
 #include <array>
@@ -440,15 +441,35 @@ constexpr double kSbvhBudget = 0.75;     // at most this many extra references p
 constexpr int kSbvhLeafMax = 0;
 constexpr long long kSbvhLeafBySize = 1ll << 18;
 
-struct SRef { uint32_t slot; V3 lo, hi; };
+// clo / chi: the clip region of the reference, the intersection of the half-spaces of the spatial
+// splits that produced it (-inf / +inf where uncut).  Invariant: for every triangle, the regions of its
+// records together cover all of R^3 (closed boxes) -- a split narrows the two halves to the two
+// sides of its plane and every other way a reference is handed down keeps its region --, so a
+// triangle that moves is still covered by the records' re-clipped boxes (rt_reclip.hpp).
+struct SRef { uint32_t slot; V3 lo, hi, clo, chi; };
+const V3 kClipLo = {-INFINITY, -INFINITY, -INFINITY}, kClipHi = {INFINITY, INFINITY, INFINITY};
+
+// Clip regions of the records of one record list: idx[record] = -1 (uncut) or the row of six doubles
+// (lo xyz, hi xyz) in box.
+struct ClipList {
+  std::vector<int32_t> idx;
+  std::vector<double> box;
+  void push(const SRef& r) {
+    if (r.clo == kClipLo && r.chi == kClipHi) { idx.push_back(-1); return; }
+    idx.push_back((int32_t)(box.size() / 6));
+    box.insert(box.end(), r.clo.begin(), r.clo.end());
+    box.insert(box.end(), r.chi.begin(), r.chi.end());
+  }
+};
 
 inline bool box_valid(const V3& lo, const V3& hi) { return lo[0] <= hi[0] && lo[1] <= hi[1] && lo[2] <= hi[2]; }
 
 // Bounds of the parts of triangle r.slot on either side of plane x[axis] = pos, each
-// intersected with r's box.  An empty side comes back with an invalid box.
+// intersected with r's box.  An empty side comes back with an invalid box.  Both inherit r's clip
+// region: only the caller that keeps both halves narrows it.
 void split_ref(const rt_scene_soa* s, const SRef& r, int axis, double pos, SRef& L, SRef& R) {
-  L = {r.slot, kV3Lo, kV3Hi};
-  R = {r.slot, kV3Lo, kV3Hi};
+  L = {r.slot, kV3Lo, kV3Hi, r.clo, r.chi};
+  R = {r.slot, kV3Lo, kV3Hi, r.clo, r.chi};
   V3 v[3];
   for (int c = 0; c < 3; ++c)
     for (int k = 0; k < 3; ++k) v[c][k] = s->vertex_pos[3 * (size_t)s->vertex_idx[3 * (size_t)r.slot + c] + k];
@@ -663,6 +684,8 @@ bool sbvh_split(const SbvhCtx& C, std::vector<SRef>& R, int depth, long long& bu
       const double c_left = half_area(ulo, uhi) * (double)nl + half_area(tlo, thi) * (double)(nr - 1);
       const double c_right = half_area(slo, shi) * (double)(nl - 1) + half_area(vlo, vhi) * (double)nr;
       if (c_split <= c_left && c_split <= c_right && budget > 0) {
+        Lp.chi[k] = std::min(Lp.chi[k], sp_pos);   // both halves kept: each record's region ends at the plane
+        Rp.clo[k] = std::max(Rp.clo[k], sp_pos);
         left.push_back(Lp); right.push_back(Rp);
         llo = slo; lhi = shi; rlo = tlo; rhi = thi;
         budget--;
@@ -690,7 +713,7 @@ bool sbvh_split(const SbvhCtx& C, std::vector<SRef>& R, int depth, long long& bu
 // Builds the subtree of references R under node `root` of T (single thread); leaves index
 // `records` (local to this subtree).
 void sbvh_subtree(const SbvhCtx& C, DevTree& T, int root, std::vector<SRef>&& R, int depth, long long budget,
-                  std::vector<uint32_t>& records) {
+                  std::vector<uint32_t>& records, ClipList& clips) {
   struct Job { int id; std::vector<SRef> refs; int depth; };
   std::vector<Job> jobs;
   jobs.push_back({root, std::move(R), depth});
@@ -706,7 +729,7 @@ void sbvh_subtree(const SbvhCtx& C, DevTree& T, int root, std::vector<SRef>&& R,
     if (!split) {   // a leaf leaves the references in place
       T.first[j.id] = (int)records.size();
       T.count[j.id] = (int)n;
-      for (const SRef& r : j.refs) records.push_back(r.slot);
+      for (const SRef& r : j.refs) { records.push_back(r.slot); clips.push(r); }
       continue;
     }
     const int l = T.add(), r = T.add();
@@ -720,7 +743,7 @@ void sbvh_subtree(const SbvhCtx& C, DevTree& T, int root, std::vector<SRef>&& R,
 }
 
 void build_sbvh_tree(const rt_scene_soa* s, const rt_upload_options& opt, DevTree& E,
-                     std::vector<uint32_t>& records) {
+                     std::vector<uint32_t>& records, ClipList& clips) {
   const bool timing = g_verbose;
   auto t_last = std::chrono::steady_clock::now();
   auto tick = [&](const char* phase) {
@@ -738,6 +761,7 @@ void build_sbvh_tree(const rt_scene_soa* s, const rt_upload_options& opt, DevTre
         SRef& r = refs[i];
         r.slot = (uint32_t)i;
         r.lo = kV3Lo; r.hi = kV3Hi;
+        r.clo = kClipLo; r.chi = kClipHi;
         for (int c = 0; c < 3; ++c) {
           const double* p = s->vertex_pos + 3 * (size_t)s->vertex_idx[3 * i + c];
           const V3 q = {p[0], p[1], p[2]};
@@ -797,6 +821,7 @@ void build_sbvh_tree(const rt_scene_soa* s, const rt_upload_options& opt, DevTre
   for (const Job& j : pending) pend_refs += (long long)j.refs.size();
   std::vector<DevTree> arena(pending.size());
   std::vector<std::vector<uint32_t>> recs(pending.size());
+  std::vector<ClipList> rclip(pending.size());
   std::vector<long long> share(pending.size());
   for (size_t k = 0; k < pending.size(); ++k)
     share[k] = pend_refs > 0 ? (long long)((double)budget * (double)pending[k].refs.size() / (double)pend_refs) : 0;
@@ -804,7 +829,7 @@ void build_sbvh_tree(const rt_scene_soa* s, const rt_upload_options& opt, DevTre
   auto worker = [&]() {
     for (size_t k; (k = next.fetch_add(1)) < pending.size();) {
       arena[k].add();
-      sbvh_subtree(C, arena[k], 0, std::move(pending[k].refs), pending[k].depth, share[k], recs[k]);
+      sbvh_subtree(C, arena[k], 0, std::move(pending[k].refs), pending[k].depth, share[k], recs[k], rclip[k]);
     }
   };
   {
@@ -815,17 +840,21 @@ void build_sbvh_tree(const rt_scene_soa* s, const rt_upload_options& opt, DevTre
   }
   tick("subtrees");
   // append in job order (thread-count independent): arena k's node i > 0 -> base[k] + i,
-  // its records -> rbase[k] + local index
-  std::vector<long long> base(pending.size()), rbase(pending.size());
-  long long total = (long long)E.left.size(), rtotal = 0;
+  // its records -> rbase[k] + local index, its clip rows -> cbase[k] + local row
+  std::vector<long long> base(pending.size()), rbase(pending.size()), cbase(pending.size());
+  long long total = (long long)E.left.size(), rtotal = 0, ctotal = 0;
   for (size_t k = 0; k < pending.size(); ++k) {
     base[k] = total - 1;
     total += (long long)arena[k].left.size() - 1;
     rbase[k] = rtotal;
     rtotal += (long long)recs[k].size();
+    cbase[k] = ctotal;
+    ctotal += (long long)rclip[k].box.size() / 6;
   }
   E.resize((size_t)total);
   records.assign((size_t)rtotal, 0);
+  clips.idx.assign((size_t)rtotal, -1);
+  clips.box.assign(6 * (size_t)ctotal, 0.0);
   next = 0;
   auto merge = [&]() {
     for (size_t k; (k = next.fetch_add(1)) < pending.size();) {
@@ -841,8 +870,12 @@ void build_sbvh_tree(const rt_scene_soa* s, const rt_upload_options& opt, DevTre
         E.right[id] = A.count[i] > 0 ? -1 : map(A.right[i]);
       }
       std::copy(recs[k].begin(), recs[k].end(), records.begin() + rbase[k]);
+      for (size_t i = 0; i < rclip[k].idx.size(); ++i)
+        if (rclip[k].idx[i] >= 0) clips.idx[(size_t)rbase[k] + i] = (int32_t)(cbase[k] + rclip[k].idx[i]);
+      std::copy(rclip[k].box.begin(), rclip[k].box.end(), clips.box.begin() + 6 * cbase[k]);
       A = DevTree();
       std::vector<uint32_t>().swap(recs[k]);
+      rclip[k] = ClipList();
     }
   };
   {
@@ -937,7 +970,7 @@ void collapse_dp(const DevTree& E, double c_tri, CollapseDp& P) {
 // Orders children, renumbers the tree in preorder (node 0 stays the root, every child id above its
 // parent's: the collapse's sweep needs it) and lays the records out in the leaves' left-to-right
 // order, so a subtree's records stay contiguous.
-void tree_opt_finish(DevTree& E, std::vector<uint32_t>& dev2slot) {
+void tree_opt_finish(DevTree& E, std::vector<uint32_t>& dev2slot, std::vector<int32_t>* dev2clip = nullptr) {
   const size_t nn = E.left.size();
 #if RT_TREE_OPT_CHILD_ORDER
   // The builders' children run low to high along their split axis, which the any-hit waves' "last
@@ -956,6 +989,7 @@ void tree_opt_finish(DevTree& E, std::vector<uint32_t>& dev2slot) {
   DevTree T;
   T.resize(nn);
   std::vector<uint32_t> recs(dev2slot.size());
+  std::vector<int32_t> crecs(dev2clip ? dev2clip->size() : 0);   // the records' clip rows move with them
   size_t nrec = 0;
   int next = 0;
   std::vector<std::pair<int, int>> stk;   // (old id, new parent id or -1; right child flagged by ~parent)
@@ -970,7 +1004,10 @@ void tree_opt_finish(DevTree& E, std::vector<uint32_t>& dev2slot) {
     T.count[id] = E.count[o];
     if (E.count[o] != 0) {
       T.first[id] = (int)nrec;
-      for (int k = 0; k < E.count[o]; ++k) recs[nrec++] = dev2slot[(size_t)E.first[o] + k];
+      for (int k = 0; k < E.count[o]; ++k) {
+        if (!crecs.empty()) crecs[nrec] = (*dev2clip)[(size_t)E.first[o] + k];
+        recs[nrec++] = dev2slot[(size_t)E.first[o] + k];
+      }
     } else {
       stk.emplace_back(E.right[o], ~id);
       stk.emplace_back(E.left[o], id);
@@ -978,6 +1015,7 @@ void tree_opt_finish(DevTree& E, std::vector<uint32_t>& dev2slot) {
   }
   E = std::move(T);
   dev2slot.swap(recs);
+  if (dev2clip) dev2clip->swap(crecs);
 }
 
 // Runs at most max_passes passes over E (children ids need not exceed their parent's afterwards:
@@ -1289,8 +1327,9 @@ int build_image(const rt_scene_soa* s, const rt_bvh_soa* b, const rt_upload_opti
   // of the triangles the ray can hit, so it does not depend on the tree.
   DevTree E;
   std::vector<uint32_t> dev2slot((size_t)std::max<long long>(nt, 1));
+  ClipList clips;   // of the records in dev2slot's order (sbvh only; empty otherwise)
   if (nt > 0) {
-    if (tree_kind == RT_TREE_SBVH) build_sbvh_tree(s, opt, E, dev2slot);
+    if (tree_kind == RT_TREE_SBVH) build_sbvh_tree(s, opt, E, dev2slot, clips);
     else if (tree_kind == RT_TREE_SAH) build_sah_tree(s, E, dev2slot);
     else build_device_tree(s, b, E, dev2slot);
   }
@@ -1317,8 +1356,9 @@ int build_image(const rt_scene_soa* s, const rt_bvh_soa* b, const rt_upload_opti
       const auto t0 = std::chrono::steady_clock::now();
       DevTree E0 = E;
       std::vector<uint32_t> d0 = dev2slot;
+      std::vector<int32_t> c0 = clips.idx;
       tree_opt_passes(E, opt.tree_opt, ostats);
-      tree_opt_finish(E, dev2slot);
+      tree_opt_finish(E, dev2slot, clips.idx.empty() ? nullptr : &clips.idx);
       collapse_dp(E, opt.collapse_c_tri, P);
       dp1 = P.D[0][1];
       sah1 = tree_sah(E);
@@ -1341,6 +1381,7 @@ int build_image(const rt_scene_soa* s, const rt_bvh_soa* b, const rt_upload_opti
       if (!kept) {
         E = std::move(E0);
         dev2slot = std::move(d0);
+        clips.idx = std::move(c0);
         collapse_dp(E, opt.collapse_c_tri, P);
         dp1 = dp0;
         sah1 = sah0;
@@ -1573,6 +1614,13 @@ int build_image(const rt_scene_soa* s, const rt_bvh_soa* b, const rt_upload_opti
   I.slot2dev = std::move(slot2dev);
   I.shade = std::move(shade);
   I.tnorm = std::move(tnorm);
+  I.clip.reset();
+  if (!clips.box.empty()) {   // compact: no table where no record was cut
+    auto tab = std::make_shared<ClipTable>();
+    tab->idx = std::move(clips.idx);
+    tab->box = std::move(clips.box);
+    I.clip = std::move(tab);
+  }
   I.mats = std::move(mats);
   I.n_tris = nt;
   I.n_vertices = s->n_vertices;
@@ -1625,4 +1673,36 @@ extern "C" int rt_debug_tree_report(const rt_scene_soa* soa, const rt_bvh_soa* b
   if (o.collapse_c_tri == 0.0) o.collapse_c_tri = d.collapse_c_tri;
   rtk::SceneImage none;
   return rtk::build_image(soa, bvh, o, 0, none, out);
+}
+
+// Host only: no HIP call (rt_hip.h).  The records' regions and slots of the image rt_scene_upload_ex
+// builds with these options.
+extern "C" long long rt_debug_clip_regions(const rt_scene_soa* soa, const rt_bvh_soa* bvh, const rt_upload_options* opt,
+                                           double* clip_out, int* slot_out, long long cap) {
+  if (cap < 0 || (cap > 0 && (!clip_out || !slot_out))) return RT_ERR_INVALID;
+  rt_upload_options o, d;
+  rtk::upload_options_defaults(&d);
+  o = opt ? *opt : d;
+  if (o.sbvh_bins == 0) o.sbvh_bins = d.sbvh_bins;
+  if (o.sbvh_c_trav == 0.0) o.sbvh_c_trav = d.sbvh_c_trav;
+  if (o.collapse_c_tri == 0.0) o.collapse_c_tri = d.collapse_c_tri;
+  rtk::SceneImage I;
+  const int rc = rtk::build_image(soa, bvh, o, 0, I);
+  if (rc != RT_OK) return rc;
+  const long long n = (long long)I.tris.size();
+  for (long long g = 0; g < std::min(n, cap); ++g) {
+    const int32_t row = I.clip ? I.clip->idx[(size_t)g] : -1;
+    for (int k = 0; k < 3; ++k) {
+      clip_out[6 * g + k] = row < 0 ? -INFINITY : I.clip->box[6 * (size_t)row + k];
+      clip_out[6 * g + 3 + k] = row < 0 ? INFINITY : I.clip->box[6 * (size_t)row + 3 + k];
+    }
+    slot_out[g] = (int)(I.tris[(size_t)g].meta & rtk::kSlotMask);
+  }
+  return n;
+}
+
+extern "C" int rt_reclip_box_host(const double p0[3], const double p1[3], const double p2[3], const double clip[6],
+                                  double lo[3], double hi[3]) {
+  if (!p0 || !p1 || !p2 || !clip || !lo || !hi) return RT_ERR_INVALID;
+  return rt_reclip_box(p0, p1, p2, clip, lo, hi) ? 1 : 0;
 }

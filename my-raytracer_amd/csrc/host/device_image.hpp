@@ -8,6 +8,7 @@
 // in device leaf order.  Built into librt_hip.so beside the kernel.
 #pragma once
 #include <cstdint>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -18,6 +19,15 @@ namespace rtk {
 
 constexpr int kMaxStackDepth = 4096;   // traversal stack entries (LDS ring + global spill)
 
+// Where the spatial splits of an RT_TREE_SBVH build cut the records: idx[record] is
+// -1 for a record that was never cut, else the row of box that holds its clip region, six doubles
+// (lo xyz, hi xyz; -inf / +inf on the sides no split bounded).  For every triangle the regions of its
+// records together cover all of space.
+struct ClipTable {
+  std::vector<int32_t> idx;   // [records]
+  std::vector<double> box;    // [6 * cut records]
+};
+
 // Host-side device layout of a scene: built once (the expensive part: device hierarchy,
 // records), then copied to any number of devices.
 struct SceneImage {
@@ -27,6 +37,7 @@ struct SceneImage {
   std::vector<uint32_t> slot2dev; // reference slot -> first device record
   std::vector<TriShade> shade;
   std::vector<double> tnorm, tu, tv;
+  std::shared_ptr<const ClipTable> clip;   // null where no record was cut (SAH / reference tree, no duplicate)
   std::vector<unsigned char> texels;
   std::vector<GMat> mats;
   long long n_tris = 0;

@@ -134,6 +134,40 @@ def tree_report(host_scene, tree=None, **options):
     return rep
 
 
+def clip_regions(host_scene, tree=None, **options):
+    """rt_debug_clip_regions of a prepared HostScene: (clip [records, 6] float64 -- lo xyz, hi xyz of
+    the region each device record was cut to, -inf / +inf where uncut --, slot [records] int32) of
+    the hierarchy these upload options give, built on the host only -- no GPU needed."""
+    fn = _update_fn("rt_debug_clip_regions")
+    opt = upload_options(tree, **options)
+    n = int(fn(host_scene.soa, host_scene.bvh, C.byref(opt), None, None, 0))
+    if n < 0:
+        raise RtError(f"rt_debug_clip_regions: error {n}")
+    clip = np.zeros((n, 6), dtype=np.float64)
+    slot = np.zeros(n, dtype=np.int32)
+    got = int(fn(host_scene.soa, host_scene.bvh, C.byref(opt), clip.ctypes.data_as(C.POINTER(C.c_double)),
+                 slot.ctypes.data_as(C.POINTER(C.c_int)), n))
+    if got != n:
+        raise RtError(f"rt_debug_clip_regions: error {got}")
+    return clip, slot
+
+
+def reclip_box_host(p0, p1, p2, clip):
+    """rt_reclip_box_host: the fp64 box the re-clipping refit gives triangle (p0, p1, p2) in region
+    clip (lo xyz, hi xyz), the device's function text run on the host.  Returns (lo, hi) float64 [3]
+    arrays, or None where nothing of the triangle's bounds is left in the region."""
+    fn = _update_fn("rt_reclip_box_host")
+    dp = C.POINTER(C.c_double)
+    a = [np.ascontiguousarray(x, dtype=np.float64).reshape(-1) for x in (p0, p1, p2, clip)]
+    if [len(x) for x in a] != [3, 3, 3, 6]:
+        raise ValueError("p0, p1, p2 must hold 3 numbers and clip 6")
+    lo, hi = np.zeros(3), np.zeros(3)
+    rc = fn(*[x.ctypes.data_as(dp) for x in a], lo.ctypes.data_as(dp), hi.ctypes.data_as(dp))
+    if rc < 0:
+        raise RtError(f"rt_reclip_box_host: error {rc}")
+    return (lo, hi) if rc == 1 else None
+
+
 def _np(ptr, count, dtype):
     if count == 0:
         return np.zeros(0, dtype=dtype)
@@ -310,26 +344,41 @@ class DeviceScene:
         _check_hip(hip_lib().rt_scene_upload_seconds(self._h, C.byref(b), C.byref(c)), "rt_scene_upload_seconds")
         return b.value, c.value
 
-    def update(self, host_scene, stream=None):
+    def update(self, host_scene, stream=None, reclip=False):
         """rt_scene_update_vertices with the three arrays of a host scene's SoA: the HostScene this
         scene was uploaded from after HostScene.update_vertices, or any prepared scene of the same
-        topology and slots."""
+        topology and slots.  reclip: as in update_vertices."""
         s = host_scene.soa.contents
         u = abi.SceneUpdate(n_vertices=s.n_vertices, n_triangles=s.n_vertex_idx // 3, vertex_pos=s.vertex_pos,
                             vertex_normals=s.vertex_normals, face_normals=s.face_normals)
-        _check_hip(_update_fn("rt_scene_update_vertices")(self._h, C.byref(u), C.c_void_p(stream) if stream else None),
-                   "rt_scene_update_vertices")
+        self._update(u, stream, reclip)
 
-    def update_vertices(self, vertex_pos, vertex_normals, face_normals, stream=None):
+    def _update(self, u, stream, reclip):
+        st = C.c_void_p(stream) if stream else None
+        if reclip:
+            _check_hip(_update_fn("rt_scene_update_vertices_ex")(self._h, C.byref(u), abi.RT_UPDATE_RECLIP, st),
+                       "rt_scene_update_vertices_ex")
+        else:
+            _check_hip(_update_fn("rt_scene_update_vertices")(self._h, C.byref(u), st), "rt_scene_update_vertices")
+
+    def update_vertices(self, vertex_pos, vertex_normals, face_normals, stream=None, reclip=False):
         """Moves the scene's vertices on the device (rt_scene_update_vertices): new positions and
         vertex normals ([n_vertices, 3] float64) and face normals ([n_triangles, 3] float64, leaf
         order of the uploaded SoA) on the uploaded topology; the triangle and normal records are
         rewritten and the 4-wide hierarchy's boxes refitted by kernels on `stream` (an int pointer,
         None = the null stream).  Afterwards every launch and query returns what a fresh upload of
         the moved scene returns, bit for bit.  The arrays may be reused when the call returns.
-        Upload a scene that will move with tree="sah": the default SBVH's clipped leaf boxes become
-        whole-triangle boxes at the first update (correct, but 29-39x slower frames on the office
-        proxy)."""
+        reclip=True (rt_scene_update_vertices_ex with RT_UPDATE_RECLIP) bounds every
+        record a spatial split of the upload cut by the part of its moved triangle inside the
+        record's clip region, so a default (SBVH) tree keeps its clipped leaves; on a scene without
+        cut records it is the plain refit.  The first such update copies the clip table to the
+        device (4 B per record + 48 B per cut record).
+        Upload a scene that will move far with tree="sah": under a plain update the default SBVH's
+        clipped leaf boxes become whole-triangle boxes (correct, but 29-39x slower frames on the
+        office proxy).  With reclip=True the office frame stays within 1.03x of a
+        fresh upload's at a displacement of 0.01 of the box diagonal and 1.5-1.8x at 0.1-0.3, where
+        the refitted SAH tree can be the faster one: never update a default tree
+        without it."""
         arrs = [np.ascontiguousarray(a, dtype=np.float64) for a in (vertex_pos, vertex_normals, face_normals)]
         for a in arrs:
             if a.ndim != 2 or a.shape[1] != 3:
@@ -339,8 +388,7 @@ class DeviceScene:
         dp = C.POINTER(C.c_double)
         u = abi.SceneUpdate(n_vertices=len(arrs[0]), n_triangles=len(arrs[2]), vertex_pos=arrs[0].ctypes.data_as(dp),
                             vertex_normals=arrs[1].ctypes.data_as(dp), face_normals=arrs[2].ctypes.data_as(dp))
-        _check_hip(_update_fn("rt_scene_update_vertices")(self._h, C.byref(u), C.c_void_p(stream) if stream else None),
-                   "rt_scene_update_vertices")
+        self._update(u, stream, reclip)
 
     def debug_scene_image(self, what):
         """Test hook (rt_debug_scene_image): the device's "nodes4" ([n, 32] uint32 view of the 128-B

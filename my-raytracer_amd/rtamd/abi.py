@@ -179,6 +179,7 @@ class CameraOut(C.Structure):
 
 
 RT_IMAGE_NODES4, RT_IMAGE_TRIS, RT_IMAGE_TNORM = 0, 1, 2
+RT_UPDATE_RECLIP = 1   # rt_scene_update_vertices_ex flag
 
 
 class SceneUpdate(C.Structure):
@@ -276,6 +277,10 @@ HIP_SYMBOLS = {
     "rt_surface_points_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_double, C.c_void_p]),
     "rt_scene_update_vertices": (C.c_int, [C.c_void_p, C.POINTER(SceneUpdate), C.c_void_p]),
     "rt_debug_scene_image": (C.c_longlong, [C.c_void_p, C.c_int, C.c_void_p, C.c_longlong]),
+    "rt_scene_update_vertices_ex": (C.c_int, [C.c_void_p, C.POINTER(SceneUpdate), C.c_uint, C.c_void_p]),
+    "rt_debug_clip_regions": (C.c_longlong, [C.POINTER(SceneSoA), C.POINTER(BvhSoA), C.POINTER(UploadOptions),
+                                             C.POINTER(C.c_double), C.POINTER(C.c_int), C.c_longlong]),
+    "rt_reclip_box_host": (C.c_int, [C.POINTER(C.c_double)] * 6),
     "rt_last_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "rt_tile_shape": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "rt_ipc_get_handle": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_ulonglong)]),
