@@ -798,6 +798,77 @@ long long rt_debug_clip_regions(const rt_scene_soa* soa, const rt_bvh_soa* bvh, 
 int rt_reclip_box_host(const double p0[3], const double p1[3], const double p2[3], const double clip[6],
                        double lo[3], double hi[3]);
 
+/* Moving a scene by positions alone: the face normals, the angle-weighted vertex
+ * normals, max|vertex| and the root box are made by kernels, from a HOST or a DEVICE array.
+ *
+ * rt_scene_set_triangle_order comes first, once per scene.  A vertex's normal sums its corners in
+ * the mesh's original triangle order, corner 0, 1, 2 within a triangle, and the uploaded scene
+ * holds its triangles in leaf-slot order: slot_triangle[slot] = the triangle's index in the
+ * original order (rt_host_slot_triangles, rt_host.h).  Host part: RT_ERR_INVALID for a NULL
+ * pointer, an array that is not a permutation of [0, n_triangles) or a count other than the
+ * scene's; RT_ERR_UNSUPPORTED where 3 * n_triangles does not fit a signed 32-bit corner index.  It
+ * reads every slot's vertex ids back from the device records and builds, on the device, the
+ * per-slot ids (16 B per slot), a CSR of every vertex's corners (slot, corner) sorted by
+ * (slot_triangle[slot], corner) -- 4 B per vertex + 4, 4 B per corner; a triangle that names a
+ * vertex twice contributes two entries -- and the corner weights (32 B per slot):
+ * rt_scene_device_bytes grows by 60 * n_triangles + 4 * (n_vertices + 1) bytes, at this call and
+ * only here (by nothing for a scene without triangles); a scene that never calls it costs what it
+ * did before.  Calling it again replaces the tables (after a device synchronisation). */
+int rt_scene_set_triangle_order(rt_scene* scene, const int* slot_triangle, long long n_triangles);
+
+typedef struct rt_scene_positions {
+  long long n_vertices;        /* must equal the uploaded scene's */
+  const double* vertex_pos;    /* [3*n_vertices], global vertex order */
+  int on_device;               /* 0: HOST pointer; 1: DEVICE pointer on the scene's device */
+  int reserved_;
+  long long reserved2_[3];
+} rt_scene_positions;
+
+/* The definition is compositional: the call has the effect of rt_host_update_vertices (rt_host.h)
+ * with these positions on the host scene this scene was uploaded from, followed by
+ * rt_scene_update_vertices_ex(scene, that scene's three arrays, flags, stream).  For finite
+ * positions this holds bit for bit: the 4-wide nodes, the triangle and the normal records
+ * (rt_debug_scene_image), delta, rt_scene_bounds and every frame, query and ray count afterwards.
+ * The normals are rt_normals.hpp's text, the one HostMesh::compute_normals runs, in fp64 + - * /
+ * sqrt with contraction off.  Positions that hold a NaN are outside the bit-for-bit contract (the
+ * payload of a generated NaN differs between host and GPU); they neither fault nor hang and are not
+ * looked for, as at upload.  flags: 0 or RT_UPDATE_RECLIP.  The two update calls may alternate in
+ * any order on one scene; RT_FLAG_TRAVERSAL_STATS stays refused after either.
+ *   Checks, before any HIP call: RT_ERR_INVALID for a NULL scene, struct or pointer, an on_device
+ * other than 0 or 1, a count other than the scene's, an unknown flag, or a scene that has had no
+ * rt_scene_set_triangle_order call; RT_ERR_HIP on a scene whose watchdog word is set.  A scene
+ * without triangles returns RT_OK without a launch (from a device pointer also without reading it:
+ * its delta stays).
+ *   on_device = 0: max|vertex|, the RT_ERR_UNSUPPORTED check (RT_MAX_COORDINATE) and the root box
+ * are taken on the host exactly as rt_scene_update_vertices_ex takes them, the positions are copied
+ * with one hipMemcpyAsync, and there is no host synchronisation: the array may be reused when the
+ * call returns, and updates and renders can be queued back to back on one stream.
+ *   on_device = 1: a reduction kernel reads the caller's buffer in stream order and writes
+ * max|vertex| over all 3 * n_vertices values and the box of the referenced vertices to page-locked
+ * host memory of the scene.  THE CALL THEN WAITS FOR THAT STREAM, ONCE -- its one synchronisation --,
+ * applies the RT_MAX_COORDINATE check (on refusal the scene is exactly as it was: nothing of it has
+ * been written by then), switches delta and the root box and issues the rest asynchronously.  The
+ * buffer may be overwritten once the work issued on `stream` has finished.  The scene's first such
+ * call copies the referenced vertex ids to the device and allocates the block partials:
+ * rt_scene_device_bytes grows by 4 * referenced vertices + 14336 bytes, then and only then.
+ *   Device part: face_normals_kernel (one thread per slot), vertex_normals_kernel (one per vertex),
+ * then the record and refit kernels of rt_scene_update_vertices, unchanged.  The stream rules and the
+ * first-use allocations are those of rt_scene_update_vertices, the CU-masked stream of
+ * rt_upload_options.reserve_cus included.
+ *   Not built: a synchronisation-free device-pointer variant (it needs caller-supplied bounds, or
+ * launches that read delta from memory); an rt_multi wrapper; topology changes; keeping the host
+ * scene in step -- the rt_host_scene, and an oracle made from it, still see the old positions. */
+int rt_scene_update_positions(rt_scene* scene, const rt_scene_positions* positions, unsigned flags, void* stream);
+
+/* Pure host, no HIP call and no scene: the normals rt_scene_update_positions makes, by the same CSR
+ * build and the same per-thread bodies.  vertex_idx [3 * n_triangles] in leaf order
+ * (rt_scene_soa.vertex_idx), slot_triangle as above, vertex_pos [3 * n_vertices];
+ * vertex_normals_out [3 * n_vertices], face_normals_out [3 * n_triangles] in leaf order.
+ * RT_ERR_INVALID for a NULL pointer, a negative count, a non-permutation or a vertex id out of
+ * range. */
+int rt_normals_host(const int* vertex_idx, const int* slot_triangle, long long n_vertices, long long n_triangles,
+                    const double* vertex_pos, double* vertex_normals_out, double* face_normals_out);
+
 /* Test hook in the style of rt_debug_counters: copies a device array of the scene's layout into
  * out[0 .. min(bytes, size)) -- RT_IMAGE_NODES4: the 4-wide nodes (128 B each: lo / hi of x, y, z
  * for 4 slots as fp32, 4 refs, 4 pad words), RT_IMAGE_TRIS: the triangle records (80 B each),

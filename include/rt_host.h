@@ -67,6 +67,13 @@ int rt_host_prepare_ex(rt_host_scene* s, int build_threads, double* seconds);
  * an n_vertices other than the scene's. */
 int rt_host_update_vertices(rt_host_scene* s, const double* vertex_pos, long long n_vertices);
 
+/* [n_triangles]: leaf slot -> triangle index in build_Data's order (the meshes' triangles
+ * concatenated), the permutation BVH::initSoA applied to the per-triangle arrays of rt_scene_soa.
+ * Valid after rt_host_prepare (NULL before) while the scene lives; rt_host_update_vertices does not
+ * change it.  It is the order rt_scene_set_triangle_order (rt_hip.h) needs: a vertex's normal sums
+ * its corners in this triangle order. */
+const int* rt_host_slot_triangles(const rt_host_scene* s);
+
 /* Valid after rt_host_prepare. */
 const rt_scene_soa* rt_host_soa(const rt_host_scene* s);
 const rt_bvh_soa* rt_host_bvh(const rt_host_scene* s);

@@ -71,6 +71,7 @@
 #include "rt_ao_fan.hpp"   // the fan of a surface point (gather_kernel below, rt_ao.inc)
 #include "rt_refit.hpp"    // records and boxes of moved vertices (rt_update.inc)
 #include "rt_reclip.hpp"   // ... and the box of a moved triangle in its record's clip region
+#include "rt_normals.hpp"  // ... and the normals of moved vertices (rt_normals.inc)
 
 using namespace rtk;
 
@@ -2744,6 +2745,7 @@ struct LaunchCtx {
 
 struct QueryRing;   // ray-query contexts (rt_query.inc)
 struct UpdateState; // device arrays and refit schedule of rt_scene_update_vertices (rt_update.inc)
+struct NormalState; // tables of the normal kernels of rt_scene_update_positions (rt_normals.inc)
 
 struct rt_scene {
   int device = 0;
@@ -2824,6 +2826,7 @@ struct rt_scene {
   long long n_vertices = 0;     // of the uploaded rt_scene_soa
   long long n_rec = 0;          // device records (d_tris, d_shade, d_tnorm)
   UpdateState* update = nullptr;   // allocated by the scene's first rt_scene_update_vertices
+  NormalState* normals = nullptr;  // allocated by rt_scene_set_triangle_order
   bool updated = false;         // the vertices were moved: d_nodes (the canonical 2-wide tree) is stale
   std::shared_ptr<const ClipTable> clip;   // host: where the upload's spatial splits cut the records (null: nowhere);
                                            // one copy among the scenes of rt_scene_upload_multi, released by rt_scene_free
@@ -3570,6 +3573,8 @@ struct StreamScratch {
 #include "rt_camera.inc"
 // moving the scene's vertices, boxes refitted on the device: rt_scene_update_vertices
 #include "rt_update.inc"
+// ... from positions alone, normals and bounds made on the device: rt_scene_update_positions
+#include "rt_normals.inc"
 
 namespace {
 // what a ray-list launch (rt_trace_radiance, rt_trace_gather) rejects about its render parameters,
@@ -4157,6 +4162,7 @@ void rt_scene_free(rt_scene* sc) {
   if (sc->h_guard) (void)hipHostFree(sc->h_guard);
   query_ring_free(sc);
   update_state_free(sc);
+  normal_state_free(sc);
   for (LaunchCtx& c : sc->ctx) {
     void* cp[] = {c.d_ctr, c.d_pstate, c.d_spill, c.d_wavelog, c.d_tl, c.d_wctr};
     for (void* q : cp)

@@ -301,6 +301,58 @@ int update_state_clip(rt_scene* sc) {
   return RT_OK;
 }
 
+// The stream a render launch given `caller` would use (reserve_cus: the caller's CU-masked stream,
+// which then waits for the work issued on `caller` so far).
+int update_stream_begin(rt_scene* sc, hipStream_t caller, hipStream_t* st) {
+  UpdateState& U = *sc->update;
+  *st = caller;
+  if (sc->reserve_cus > 0) {
+    const int mrc = masked_stream(sc, caller, st);
+    if (mrc != RT_OK) return mrc;
+    if (!U.ev_in) HIP_TRY(hipEventCreateWithFlags(&U.ev_in, hipEventDisableTiming));
+    if (!U.ev_out) HIP_TRY(hipEventCreateWithFlags(&U.ev_out, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(U.ev_in, caller));
+    HIP_TRY(hipStreamWaitEvent(*st, U.ev_in, 0));
+  }
+  return RT_OK;
+}
+
+// With d_vpos, d_vnorm and d_fnorm written in the order of `st`: one kernel rewrites the records, one
+// per height of the tree refits the boxes (leaf-only nodes first), `caller` is joined, and the
+// scene's delta and root box ([lo, hi] grown by delta) switch.
+int update_issue(rt_scene* sc, hipStream_t st, hipStream_t caller, bool reclip, double delta, const double lo[3],
+                 const double hi[3]) {
+  UpdateState& U = *sc->update;
+  const long long n_rec = sc->n_rec;
+  hipLaunchKernelGGL(update_records_kernel, dim3((unsigned)((n_rec + kUpdBlock - 1) / kUpdBlock)), dim3(kUpdBlock), 0, st,
+                     sc->d_tris, sc->d_shade, sc->d_tnorm, U.d_vpos, U.d_vnorm, U.d_fnorm, n_rec);
+  HIP_TRY(hipGetLastError());
+  for (size_t h = 0; h + 1 < U.level_begin.size(); ++h) {   // leaf-only nodes first
+    const long long n_level = U.level_begin[h + 1] - U.level_begin[h];
+    if (n_level <= 0) continue;
+    const dim3 grid((unsigned)((4 * n_level + kUpdBlock - 1) / kUpdBlock));
+    if (reclip)
+      hipLaunchKernelGGL(reclip_nodes4_kernel, grid, dim3(kUpdBlock), 0, st, sc->d_nodes4, (uint32_t)sc->n_gnodes4,
+                         U.d_order + U.level_begin[h], n_level, sc->d_tris, sc->d_shade, n_rec, U.d_vpos, delta,
+                         U.d_clip_idx, U.d_clip_box);
+    else
+      hipLaunchKernelGGL(refit_nodes4_kernel, grid, dim3(kUpdBlock), 0, st, sc->d_nodes4, (uint32_t)sc->n_gnodes4,
+                         U.d_order + U.level_begin[h], n_level, sc->d_tris, sc->d_shade, n_rec, U.d_vpos, delta);
+    HIP_TRY(hipGetLastError());
+  }
+  if (st != caller) {   // the caller's later work follows the update
+    HIP_TRY(hipEventRecord(U.ev_out, st));
+    HIP_TRY(hipStreamWaitEvent(caller, U.ev_out, 0));
+  }
+  sc->delta = delta;
+  for (int k = 0; k < 3; ++k) {
+    sc->root_lo[k] = lo[k] - delta;
+    sc->root_hi[k] = hi[k] + delta;
+  }
+  sc->updated = true;
+  return RT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -346,50 +398,16 @@ int rt_scene_update_vertices_ex(rt_scene* sc, const rt_scene_update* u, unsigned
   double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
   for (const int v : U.used_vertices) rt_refit_grow(lo, hi, u->vertex_pos + 3 * (size_t)v);
 
-  // the stream a render launch given `stream` would use (reserve_cus: the caller's masked stream)
   const hipStream_t caller = reinterpret_cast<hipStream_t>(stream);
   hipStream_t st = caller;
-  if (sc->reserve_cus > 0) {
-    const int mrc = masked_stream(sc, caller, &st);
-    if (mrc != RT_OK) return mrc;
-    if (!U.ev_in) HIP_TRY(hipEventCreateWithFlags(&U.ev_in, hipEventDisableTiming));
-    if (!U.ev_out) HIP_TRY(hipEventCreateWithFlags(&U.ev_out, hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(U.ev_in, caller));
-    HIP_TRY(hipStreamWaitEvent(st, U.ev_in, 0));
-  }
+  const int src = update_stream_begin(sc, caller, &st);
+  if (src != RT_OK) return src;
   const size_t vb = 3 * (size_t)sc->n_vertices * sizeof(double), fb = 3 * (size_t)sc->n_tris * sizeof(double);
   // (pageable host memory: these return once the arrays were read)
   HIP_TRY(hipMemcpyAsync(U.d_vpos, u->vertex_pos, vb, hipMemcpyHostToDevice, st));
   HIP_TRY(hipMemcpyAsync(U.d_vnorm, u->vertex_normals, vb, hipMemcpyHostToDevice, st));
   HIP_TRY(hipMemcpyAsync(U.d_fnorm, u->face_normals, fb, hipMemcpyHostToDevice, st));
-  const long long n_rec = sc->n_rec;
-  hipLaunchKernelGGL(update_records_kernel, dim3((unsigned)((n_rec + kUpdBlock - 1) / kUpdBlock)), dim3(kUpdBlock), 0, st,
-                     sc->d_tris, sc->d_shade, sc->d_tnorm, U.d_vpos, U.d_vnorm, U.d_fnorm, n_rec);
-  HIP_TRY(hipGetLastError());
-  for (size_t h = 0; h + 1 < U.level_begin.size(); ++h) {   // leaf-only nodes first
-    const long long n_level = U.level_begin[h + 1] - U.level_begin[h];
-    if (n_level <= 0) continue;
-    const dim3 grid((unsigned)((4 * n_level + kUpdBlock - 1) / kUpdBlock));
-    if (reclip)
-      hipLaunchKernelGGL(reclip_nodes4_kernel, grid, dim3(kUpdBlock), 0, st, sc->d_nodes4, (uint32_t)sc->n_gnodes4,
-                         U.d_order + U.level_begin[h], n_level, sc->d_tris, sc->d_shade, n_rec, U.d_vpos, delta,
-                         U.d_clip_idx, U.d_clip_box);
-    else
-      hipLaunchKernelGGL(refit_nodes4_kernel, grid, dim3(kUpdBlock), 0, st, sc->d_nodes4, (uint32_t)sc->n_gnodes4,
-                         U.d_order + U.level_begin[h], n_level, sc->d_tris, sc->d_shade, n_rec, U.d_vpos, delta);
-    HIP_TRY(hipGetLastError());
-  }
-  if (st != caller) {   // the caller's later work follows the update
-    HIP_TRY(hipEventRecord(U.ev_out, st));
-    HIP_TRY(hipStreamWaitEvent(caller, U.ev_out, 0));
-  }
-  sc->delta = delta;
-  for (int k = 0; k < 3; ++k) {
-    sc->root_lo[k] = lo[k] - delta;
-    sc->root_hi[k] = hi[k] + delta;
-  }
-  sc->updated = true;
-  return RT_OK;
+  return update_issue(sc, st, caller, reclip, delta, lo, hi);
 }
 
 long long rt_debug_scene_image(rt_scene* sc, int what, void* out, long long bytes) {

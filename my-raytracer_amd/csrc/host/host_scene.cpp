@@ -9,6 +9,7 @@
 // arrays are reproduced exactly (tests/test_host_parity.py compares them with
 // the oracle bit for bit).
 #include "host_scene.hpp"
+#include "../device/rt_normals.hpp"
 
 #include <algorithm>
 #include <cfloat>
@@ -50,41 +51,20 @@ rt_material make_material(double ar, double ag, double ab, double dr, double dg,
 }
 
 // Angle-weighted vertex normals, mymesh.cpp:103-163: face normal
-// normalize(cross(p1-p0, p2-p0)); each corner adds n / (|u||v| + u.v).
+// normalize(cross(p1-p0, p2-p0)); each corner adds n / (|u||v| + u.v).  The arithmetic is
+// rt_normals.hpp's, the text the device runs (rt_scene_update_positions).
 void HostMesh::compute_normals() {
-  const double eps = 1e-12;
   const int nv = n_vertices(), nt = n_triangles();
   vertex_normals.assign(3 * (size_t)nv, 0.0);
   face_normals.assign(3 * (size_t)nt, 0.0);
   for (int t = 0; t < nt; ++t) {
-    const double* p0 = &positions[3 * (size_t)tri_vertex[3 * t]];
-    const double* p1 = &positions[3 * (size_t)tri_vertex[3 * t + 1]];
-    const double* p2 = &positions[3 * (size_t)tri_vertex[3 * t + 2]];
-    const double e1[3] = {p1[0] - p0[0], p1[1] - p0[1], p1[2] - p0[2]};
-    const double e2[3] = {p2[0] - p0[0], p2[1] - p0[1], p2[2] - p0[2]};
+    const int i[3] = {tri_vertex[3 * t], tri_vertex[3 * t + 1], tri_vertex[3 * t + 2]};
     double* n = &face_normals[3 * (size_t)t];
-    cross3(e1, e2, n);
-    normalize3(n);
+    double w[3];
+    rt_normals_face(&positions[3 * (size_t)i[0]], &positions[3 * (size_t)i[1]], &positions[3 * (size_t)i[2]], n, w);
+    for (int c = 0; c < 3; ++c) rt_normals_add(&vertex_normals[3 * (size_t)i[c]], n, w[c]);
   }
-  for (int t = 0; t < nt; ++t) {
-    const int i0 = tri_vertex[3 * t], i1 = tri_vertex[3 * t + 1], i2 = tri_vertex[3 * t + 2];
-    const double* p0 = &positions[3 * (size_t)i0];
-    const double* p1 = &positions[3 * (size_t)i1];
-    const double* p2 = &positions[3 * (size_t)i2];
-    const double a[3] = {p1[0] - p0[0], p1[1] - p0[1], p1[2] - p0[2]};   // v0
-    const double b[3] = {p2[0] - p1[0], p2[1] - p1[1], p2[2] - p1[2]};   // v1
-    const double c[3] = {p0[0] - p2[0], p0[1] - p2[1], p0[2] - p2[2]};   // v2
-    const double na[3] = {-a[0], -a[1], -a[2]}, nb[3] = {-b[0], -b[1], -b[2]}, nc[3] = {-c[0], -c[1], -c[2]};
-    const double la = norm3(a), lb = norm3(b), lc = norm3(c);
-    const double w0 = la * lc + dot3(a, nc);
-    const double w1 = lb * la + dot3(b, na);
-    const double w2 = lc * lb + dot3(c, nb);
-    const double* n = &face_normals[3 * (size_t)t];
-    if (std::fabs(w0) > eps) for (int k = 0; k < 3; ++k) vertex_normals[3 * (size_t)i0 + k] += n[k] / w0;
-    if (std::fabs(w1) > eps) for (int k = 0; k < 3; ++k) vertex_normals[3 * (size_t)i1 + k] += n[k] / w1;
-    if (std::fabs(w2) > eps) for (int k = 0; k < 3; ++k) vertex_normals[3 * (size_t)i2 + k] += n[k] / w2;
-  }
-  for (int v = 0; v < nv; ++v) normalize3(&vertex_normals[3 * (size_t)v]);
+  for (int v = 0; v < nv; ++v) rt_normals_normalize(&vertex_normals[3 * (size_t)v]);
 }
 
 long long HostScene::triangle_count() const {
@@ -584,6 +564,10 @@ int rt_host_update_vertices(rt_host_scene* s, const double* vertex_pos, long lon
     return host_fail("rt_host_update_vertices: n_vertices differs from the scene's");
   if (!s->scene.update_vertices(vertex_pos, n_vertices)) return host_fail("rt_host_update_vertices: failed");
   return RT_OK;
+}
+
+const int* rt_host_slot_triangles(const rt_host_scene* s) {
+  return (s && s->scene.prepared) ? s->scene.soa.slot_tri.data() : nullptr;
 }
 
 const rt_scene_soa* rt_host_soa(const rt_host_scene* s) {

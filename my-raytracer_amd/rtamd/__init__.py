@@ -230,6 +230,16 @@ class HostScene:
         _check_host(host_lib().rt_host_update_vertices(self.handle, pos.ctypes.data_as(C.POINTER(C.c_double)),
                                                        len(pos)), "update_vertices")
 
+    def slot_triangles(self):
+        """rt_host_slot_triangles: [n_triangles] int32, leaf slot -> triangle index in the original
+        order (the meshes' triangles concatenated); what DeviceScene.set_triangle_order takes.  A
+        copy; update_vertices does not change it."""
+        p = host_lib().rt_host_slot_triangles(self.handle)
+        n = self.soa.contents.n_vertex_idx // 3
+        if n and not p:
+            raise RtError("scene not prepared")
+        return _np(p, n, np.int32).copy()
+
     @property
     def raw(self):
         return host_lib().rt_host_raw(self.handle)
@@ -389,6 +399,46 @@ class DeviceScene:
         u = abi.SceneUpdate(n_vertices=len(arrs[0]), n_triangles=len(arrs[2]), vertex_pos=arrs[0].ctypes.data_as(dp),
                             vertex_normals=arrs[1].ctypes.data_as(dp), face_normals=arrs[2].ctypes.data_as(dp))
         self._update(u, stream, reclip)
+
+    def set_triangle_order(self, order):
+        """rt_scene_set_triangle_order: order[slot] = the triangle's index in the mesh's original
+        order, an int32 array such as HostScene.slot_triangles().  Once per scene, before
+        update_positions; device_bytes grows by 60 B per triangle + 4 B per vertex + 4."""
+        order = np.ascontiguousarray(order, dtype=np.int32)
+        if order.ndim != 1:
+            raise ValueError("order must be a one-dimensional int32 array")
+        _check_hip(_update_fn("rt_scene_set_triangle_order")(self._h, order.ctypes.data_as(C.POINTER(C.c_int)),
+                                                             len(order)), "rt_scene_set_triangle_order")
+
+    def update_positions(self, pos, stream=None, reclip=False):
+        """rt_scene_update_positions: moves the scene's vertices to pos, positions alone -- the face
+        and vertex normals, max|vertex| and the root box are made on the device, bit for bit what
+        HostScene.update_vertices + update() give.  pos: an [n_vertices, 3] float64
+        numpy array (the host path: no synchronisation, the array may be reused at once) or a
+        contiguous [n_vertices, 3] float64 torch tensor on this scene's device (the device path: no
+        copy through the host; the call waits for the stream once, for max|vertex| and the box).  A
+        tensor on another device, another dtype or another shape raises ValueError.  With an explicit
+        `stream`, torch's current stream is synchronised first: the tensor was produced there.  Needs
+        set_triangle_order.  reclip: as in update_vertices."""
+        on_device = hasattr(pos, "data_ptr")   # a torch tensor
+        if on_device:
+            import torch
+            dev = torch.device(f"cuda:{self.device}")
+            if not (pos.is_cuda and pos.device == dev and pos.dtype == torch.float64 and pos.dim() == 2
+                    and pos.shape[1] == 3 and pos.is_contiguous()):
+                raise ValueError(f"pos must be a contiguous [n_vertices, 3] float64 tensor on {dev}")
+            if stream:   # pos was made on torch's current stream
+                torch.cuda.current_stream(dev).synchronize()
+            addr = pos.data_ptr() if pos.shape[0] else None
+        else:
+            pos = np.ascontiguousarray(pos, dtype=np.float64)
+            if pos.ndim != 2 or pos.shape[1] != 3:
+                raise ValueError("pos must be an [n_vertices, 3] float64 array")
+            addr = pos.ctypes.data
+        p = abi.ScenePositions(n_vertices=int(pos.shape[0]), vertex_pos=addr, on_device=int(on_device))
+        _check_hip(_update_fn("rt_scene_update_positions")(self._h, C.byref(p), abi.RT_UPDATE_RECLIP if reclip else 0,
+                                                           C.c_void_p(stream) if stream else None),
+                   "rt_scene_update_positions")
 
     def debug_scene_image(self, what):
         """Test hook (rt_debug_scene_image): the device's "nodes4" ([n, 32] uint32 view of the 128-B

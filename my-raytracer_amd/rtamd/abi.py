@@ -189,6 +189,13 @@ class SceneUpdate(C.Structure):
                 ("reserved_", C.c_longlong * 3)]
 
 
+class ScenePositions(C.Structure):
+    """rt_scene_positions: the positions of rt_scene_update_positions, a HOST or a DEVICE pointer
+    (vertex_pos is a plain address: a device pointer is not dereferenced on the host)."""
+    _fields_ = [("n_vertices", C.c_longlong), ("vertex_pos", C.c_void_p), ("on_device", C.c_int),
+                ("reserved_", C.c_int), ("reserved2_", C.c_longlong * 3)]
+
+
 class GenParams(C.Structure):
     _fields_ = [("width", C.c_int), ("height", C.c_int), ("n_triangles", C.c_longlong),
                 ("seed", C.c_ulonglong), ("max_depth", C.c_int), ("detail", C.c_int)]
@@ -281,6 +288,10 @@ HIP_SYMBOLS = {
     "rt_debug_clip_regions": (C.c_longlong, [C.POINTER(SceneSoA), C.POINTER(BvhSoA), C.POINTER(UploadOptions),
                                              C.POINTER(C.c_double), C.POINTER(C.c_int), C.c_longlong]),
     "rt_reclip_box_host": (C.c_int, [C.POINTER(C.c_double)] * 6),
+    "rt_scene_set_triangle_order": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_longlong]),
+    "rt_scene_update_positions": (C.c_int, [C.c_void_p, C.POINTER(ScenePositions), C.c_uint, C.c_void_p]),
+    "rt_normals_host": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_longlong, C.c_longlong,
+                                  C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "rt_last_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "rt_tile_shape": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "rt_ipc_get_handle": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_ulonglong)]),
@@ -310,6 +321,7 @@ HOST_SYMBOLS = {
     "rt_host_prepare": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     "rt_host_prepare_ex": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double)]),
     "rt_host_update_vertices": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_longlong]),
+    "rt_host_slot_triangles": (C.POINTER(C.c_int), [C.c_void_p]),
     "rt_host_soa": (C.POINTER(SceneSoA), [C.c_void_p]),
     "rt_host_bvh": (C.POINTER(BvhSoA), [C.c_void_p]),
     "rt_host_camera": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(Camera)]),
