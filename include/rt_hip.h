@@ -706,6 +706,42 @@ int rt_camera_rays_host(const rt_render_params* p, int order, rt_ray* rays_out);
 int rt_surface_points_host(const rt_ray* rays, const rt_hit* hits, long long n, double point_tmax,
                            rt_ray* points_out);
 
+/* The k nearest hits of each ray, resumable past k: the hits behind the first one
+ * -- thickness sampling, counting the surfaces a ray crosses, picking through a pane, depth
+ * peeling, every wall between two points -- without re-tracing from pushed origins.
+ *   The definition does not depend on the hierarchy.  The ray is normalised and judged degenerate
+ * exactly as for rt_trace_closest.  Its hit list H is every reference slot whose triangle the CPU's
+ * intersect_triangle accepts with 1e-5 < t < tmax (t = DBL_MAX is never a hit), each slot once,
+ * however many device records an SBVH made of it, sorted ascending by (t, slot).  With d_after,
+ * only the entries with t > after.t || (t == after.t && slot > after.slot) belong to H: {-inf, -1}
+ * is no constraint, a NaN after.t empties the list by that comparison (nothing is special-cased),
+ * reserved_ is ignored.
+ *   d_count[i] = min(|H|, k).  d_hits[i*k + j], j < d_count[i], is the rt_hit of H[j] with the
+ * fields and bits rt_trace_closest would give that triangle (t, alpha, beta, normal by draw mode,
+ * slot, mesh, prim = -1); the rows j >= d_count[i] are the miss record: the whole buffer is
+ * defined.  d_count[i] == k means the list may go on: resume with d_after[i] = {t, slot} of the
+ * last entry; a resumed call on an exhausted list returns count 0.  There is deliberately no
+ * "more" flag: an exact one would forbid pruning at the k-th hit.  So k = 1 without d_after equals
+ * rt_trace_closest on all 64 bytes of every row, and the concatenation of resumed rounds at any k
+ * equals H.
+ *   RT_ERR_INVALID, before any HIP call, for: a NULL scene; n < 0; k outside [1, RT_HITS_MAX_K];
+ * n * k > RT_HITS_MAX_ROWS; n > 0 with a NULL d_rays, d_hits or d_count.  n == 0 returns RT_OK
+ * without a launch and touches nothing.  RT_ERR_UNSUPPORTED on a scene that holds analytic
+ * primitives (rt_scene_set_analytic with n > 0): a sphere has a second intersection that neither
+ * the reference nor the oracle defines.  RT_ERR_HIP on a scene whose watchdog word is set.
+ *   It takes a query context, as rt_trace_closest does: it runs beside renders and other queries
+ * on other streams, follows scene updates in stream order and allocates nothing beyond the
+ * contexts' first-use allocation.  Asynchronous unless stats != NULL: rays = n, hits = the sum of
+ * the counts, stack_spills and watchdog as for the queries. */
+#define RT_HITS_MAX_K 8
+#define RT_HITS_MAX_ROWS (1LL << 31)             /* n * k */
+typedef struct rt_hit_key { double t; int slot; int reserved_; } rt_hit_key;   /* 16 B */
+int rt_trace_hits(rt_scene* scene, const rt_ray* d_rays, long long n, int k,
+                  const rt_hit_key* d_after,      /* DEVICE [n], optional (NULL: none) */
+                  rt_hit* d_hits,                 /* DEVICE [n][k] */
+                  unsigned int* d_count,          /* DEVICE [n] */
+                  rt_query_stats* stats, void* stream);
+
 /* Moving geometry: new vertex positions and normals on the uploaded topology, the
  * device hierarchy refitted on the GPU -- a door that opens, a character that walks, a mesh that
  * deforms -- without rt_scene_free + rt_scene_upload_ex and their host build.  The three arrays are

@@ -3565,6 +3565,8 @@ struct StreamScratch {
 
 // batched ray queries on the device scene: kernels, query contexts, rt_trace_closest / rt_trace_occluded
 #include "rt_query.inc"
+// the k nearest hits of each ray, resumable past k: rt_trace_hits
+#include "rt_hits.inc"
 // sorting caller-supplied rays into coherent waves: rt_ray_order, rt_permute_rows
 #include "rt_order.inc"
 // occlusion fans generated on the device: rt_trace_ao, rt_ao_rays_host

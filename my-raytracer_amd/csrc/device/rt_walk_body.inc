@@ -25,6 +25,13 @@
 //   best, best_slot, best_mesh, best_a, best_b   closest hit: the record (kPrimHit | k for an
 //                analytic primitive), its reference slot, mesh and barycentrics; best == kNoHit: a miss
 //   occluded     bool: the any-hit answer
+// With RT_WALK_KHITS defined before the #include (hits_kernel, rt_hits.inc, alone: the text the other
+// kernels compile is unchanged) an accepted triangle goes into the lane's k-buffer instead of `best`,
+// and the analytic primitives are left out.  Then also expected in scope, ANYHIT being false:
+//   kh_after_t, kh_after_slot   double, int: the resume key (-inf, -1: none)
+//   kh_full      bool: the buffer holds k entries
+//   kh_last_t    double: then its last entry's t
+//   kh_insert(t, slot, record) -> bool: keeps the candidate if it belongs; true = the bound moved
     // degenerate rays are misses and are never traversed
     const double dlen = sqrt(dot(dv, dv));
     const bool act = act0 && q_finite(ro.x) && q_finite(ro.y) && q_finite(ro.z) && q_finite(dv.x) &&
@@ -39,6 +46,7 @@
     double t_off = 0.0;
     // analytic primitives first, in scene order (oracle intersect_scene): only a strictly closer
     // triangle replaces them; an occlusion ray they block skips the hierarchy
+#ifndef RT_WALK_KHITS   // (a hit list holds triangles only: rt_trace_hits refuses a scene with primitives)
     for (int k = 0; k < P.n_prims; ++k) {
       if (!act || occluded) break;
       const double t = prim_hit(P.prims[k], ro, rd);
@@ -49,6 +57,7 @@
         best_slot = -1;
       }
     }
+#endif
     if (act && P.n_gnodes > 0 && !occluded) {   // conservative fp32 box ray (oracle gray_setup)
       bool miss = false;
       const double o3[3] = {ro.x, ro.y, ro.z}, d3v[3] = {rd.x, rd.y, rd.z};
@@ -149,7 +158,13 @@
           if (!out) {
             const double Dt = det3(T.e1, T.e2, c4);
             const double t = Dt / S;
+#ifdef RT_WALK_KHITS
+            // past the resume key, and inside tmax (exclusive) or the full buffer's last t (inclusive:
+            // an equal t still reaches the slot tie-break)
+            const bool cand = (kh_full ? t <= tlim : t < tlim) && (t > kh_after_t || (t == kh_after_t && slot > kh_after_slot));
+#else
             const bool cand = ANYHIT ? (t < tlim) : (t <= tlim);
+#endif
             if (t > 1e-5 && cand) {
               double alpha, beta;
               // one reciprocal of S for both quotients where that is bit-identical (rt_render.hip)
@@ -167,6 +182,13 @@
                               (0.0 <= gamma && gamma <= 1.0);
               if (in) {
                 if (ANYHIT) return true;
+#ifdef RT_WALK_KHITS
+                // into the lane's k-buffer (rt_hits.inc); once it is full its last t is the far bound
+                if (kh_insert(t, slot, i)) {
+                  tlim = kh_last_t;
+                  hi_c = round_up_f(tlim - t_off);
+                }
+#else
                 // strictly closer, or a tie with an earlier hit: smallest reference slot
                 if (t < tlim || (best != kNoHit && slot < best_slot)) {
                   tlim = t;
@@ -177,6 +199,7 @@
                   best_b = beta;
                   hi_c = round_up_f(tlim - t_off);
                 }
+#endif
               }
             }
           }

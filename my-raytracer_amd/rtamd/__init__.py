@@ -687,6 +687,123 @@ class DeviceScene:
                 res = {k: v.numpy() for k, v in res.items()}
         return (res, st) if stats else res
 
+    def hits(self, rays, k, after=None, stats=False, stream=None):
+        """The k nearest hits of each ray (rt_trace_hits): the ray's hit list -- every triangle it
+        crosses with 1e-5 < t < tmax, each once, ascending by (t, slot) -- cut after k entries.  rays
+        as for trace(): [n, 8] float64 rows, a CUDA tensor on the scene's device, used in place, or a
+        numpy array, uploaded.  Returns a dict of [n, k] views (t, alpha, beta, normal [n, k, 3], and
+        slot, mesh, prim as int32) over one [n, k, 8] float64 result buffer of rt_hit rows, plus
+        count, an int32 [n]: the entries of a ray that are hits; the others are miss records.
+        count == k means the list may go on: call again with after = the last entry's key.
+        after: the resume keys, only hits with (t, slot) greater than a ray's key are listed.  Either
+        a pair (t, slot) of [n] arrays or tensors (float64 and integer), or one [n] numpy array of
+        rtamd.HIT_KEY_DTYPE, or one [n, 2] float64 tensor / array whose rows are rt_hit_key records
+        (t, then slot and a reserved int32 sharing the second word), used in place when it is a
+        contiguous tensor on the device.  (-inf, -1) constrains nothing; a NaN t lists nothing.
+        Tensors in, tensors out (asynchronous on `stream`, an int pointer, None = the null stream,
+        unless stats=True, or a stream together with an `after` that had to be copied); numpy in,
+        numpy out.  stats=True returns (result, QueryStats).  A scene with analytic primitives is
+        refused (RtError)."""
+        import torch
+
+        host_in = isinstance(rays, np.ndarray)
+        rays = self._hits_rays(rays)
+        n = rays.shape[0]
+        keys = None if after is None else _hit_keys(after, n, rays.device)
+        st = abi.QueryStats() if stats else None
+        out, count = self._hits_launch(rays, k, keys, st, stream)
+        if stream and keys is not None and not (isinstance(after, torch.Tensor) and after.data_ptr() == keys.data_ptr()):
+            torch.cuda.ExternalStream(stream, device=rays.device).synchronize()   # the key copy is a torch temporary
+        if host_in:
+            torch.cuda.synchronize(rays.device)
+            out, count = out.cpu(), count.cpu()
+        res = _hit_views(out.view(n * int(k), 8))
+        res = {name: v.view((n, int(k)) + tuple(v.shape[1:])) for name, v in res.items()}
+        res["count"] = count
+        if host_in:
+            res = {name: v.numpy() for name, v in res.items()}
+        return (res, st) if stats else res
+
+    def _hits_rays(self, rays):
+        """hits / all_hits `rays` argument -> contiguous [n, 8] float64 tensor on the device."""
+        import torch
+
+        dev = torch.device(f"cuda:{self.device}")
+        if isinstance(rays, np.ndarray):
+            if rays.ndim != 2 or rays.shape[1] != 8:
+                raise ValueError("rays must be an [n, 8] float64 array")
+            rays = torch.from_numpy(np.ascontiguousarray(rays, dtype=np.float64)).to(dev)
+        if not (isinstance(rays, torch.Tensor) and rays.dtype == torch.float64 and rays.dim() == 2
+                and rays.shape[1] == 8 and rays.is_contiguous() and rays.device == dev):
+            raise ValueError(f"rays must be a contiguous [n, 8] float64 tensor on {dev}")
+        return rays
+
+    def _hits_launch(self, rays, k, keys, st, stream):
+        """One rt_trace_hits call: (the [n, k, 8] float64 buffer of rt_hit rows, count int32 [n]).
+        keys: None or an [n, 2] int64 tensor of rt_hit_key records on the device."""
+        import torch
+
+        fn = _hits_fn("rt_trace_hits")
+        dev = rays.device
+        n, k = rays.shape[0], int(k)
+        if not 1 <= k <= abi.RT_HITS_MAX_K:
+            raise ValueError("k must be in [1, RT_HITS_MAX_K]")
+        if n * k > abi.RT_HITS_MAX_ROWS:
+            raise ValueError("n * k exceeds RT_HITS_MAX_ROWS")
+        out = torch.zeros((n, k, 8), dtype=torch.float64, device=dev)
+        count = torch.zeros((n,), dtype=torch.int32, device=dev)
+        if stream:   # the buffers above (and the keys) were made on torch's current stream
+            torch.cuda.current_stream(dev).synchronize()
+        _check_hip(fn(self._h, C.c_void_p(rays.data_ptr() if n else None), n, k,
+                      C.c_void_p(keys.data_ptr() if keys is not None and n else None),
+                      C.c_void_p(out.data_ptr() if n else None), C.c_void_p(count.data_ptr() if n else None),
+                      C.byref(st) if st is not None else None, C.c_void_p(stream) if stream else None), "rt_trace_hits")
+        return out, count
+
+    def all_hits(self, rays, k=8):
+        """Every hit of every ray (the whole hit list of hits()), by rounds of hits(k): after each
+        round the rays whose count is k are compacted on the device, their resume keys taken from
+        their last entry, and traced again, until none is left.  Returns a dict in CSR form:
+        offsets, an int64 [n + 1] (ray i's hits are the entries offsets[i] .. offsets[i + 1]), and
+        the flat arrays t, alpha, beta, normal [m, 3], slot, mesh, prim in ray order, each ray's
+        ascending by (t, slot).  rays as for hits(); tensors in, tensors out (the call synchronises);
+        numpy in, numpy out."""
+        import torch
+
+        host_in = isinstance(rays, np.ndarray)
+        cur = self._hits_rays(rays)
+        dev = cur.device
+        n, k = cur.shape[0], int(k)
+        live = torch.arange(n, dtype=torch.int64, device=dev)   # the rays of this round
+        keys = None
+        col = torch.arange(k, device=dev)[None, :]
+        rows, owner = [], []   # per round: the hit rows [m, 8] and the ray each belongs to
+        while live.numel() > 0:
+            out, cnt = self._hits_launch(cur, k, keys, None, None)
+            kept = col < cnt[:, None]
+            rows.append(out[kept])   # row-major: ray by ray, entry by entry
+            owner.append(live[:, None].expand(-1, k)[kept])
+            more = cnt == k
+            if not bool(more.any()):
+                break
+            # the last entry of the rays that go on: words 0 (t) and 6 (slot | mesh) are an rt_hit_key
+            keys = out.view(torch.int64)[more][:, k - 1, :][:, [0, 6]].contiguous()
+            cur = cur[more].contiguous()
+            live = live[more]
+        flat = torch.cat(rows) if rows else torch.zeros((0, 8), dtype=torch.float64, device=dev)
+        own = torch.cat(owner) if owner else torch.zeros((0,), dtype=torch.int64, device=dev)
+        # a ray's later rounds hold its later hits: a stable sort by ray puts the list in order
+        flat = flat[torch.sort(own, stable=True).indices].contiguous()
+        offsets = torch.zeros((n + 1,), dtype=torch.int64, device=dev)
+        if own.numel():
+            offsets[1:] = torch.cumsum(torch.bincount(own, minlength=n), 0)
+        res = _hit_views(flat)
+        res["offsets"] = offsets
+        torch.cuda.synchronize(dev)
+        if host_in:
+            res = {name: v.cpu().numpy() for name, v in res.items()}
+        return res
+
     def radiance(self, rays, params, stats=False, stream=None, order=None):
         """Colours of the caller's rays (rt_trace_radiance): what a pixel whose one primary ray is
         rays[i] would hold, shaded by the render kernel with params' lights, max_depth, background,
@@ -963,6 +1080,49 @@ def _hit_views(out):
     ints = out.view(torch.int32)
     return {"t": out[:, 0], "alpha": out[:, 1], "beta": out[:, 2], "normal": out[:, 3:6],
             "slot": ints[:, 12], "mesh": ints[:, 13], "prim": ints[:, 14]}
+
+
+HIT_KEY_DTYPE = np.dtype([("t", "<f8"), ("slot", "<i4"), ("reserved_", "<i4")])   # abi.HitKey rows
+
+
+def _hit_keys(after, n, dev):
+    """hits() `after` argument -> contiguous [n, 2] int64 tensor of rt_hit_key records on dev."""
+    import torch
+
+    if isinstance(after, (tuple, list)):
+        if len(after) != 2:
+            raise ValueError("after must be a pair (t, slot), a HIT_KEY_DTYPE array or [n, 2] key rows")
+        t, slot = after
+        if isinstance(t, torch.Tensor) or isinstance(slot, torch.Tensor):
+            t = torch.as_tensor(t, dtype=torch.float64, device=dev).reshape(-1).contiguous()
+            slot = torch.as_tensor(slot, device=dev).reshape(-1).to(torch.int64)
+            if t.shape[0] != n or slot.shape[0] != n:
+                raise ValueError(f"after must hold {n} keys")
+            return torch.stack([t.view(torch.int64), slot & 0xFFFFFFFF], dim=1).contiguous()
+        rec = np.zeros(np.shape(t), dtype=HIT_KEY_DTYPE)
+        rec["t"], rec["slot"] = t, slot
+        after = rec
+    if isinstance(after, np.ndarray):
+        if after.dtype == HIT_KEY_DTYPE and after.shape == (n,):
+            words = np.ascontiguousarray(after).view(np.int64).reshape(n, 2)
+        elif after.dtype == np.float64 and after.shape == (n, 2):
+            words = np.ascontiguousarray(after).view(np.int64)
+        else:
+            raise ValueError(f"after must be {n} keys: a HIT_KEY_DTYPE array [n] or float64 rows [n, 2]")
+        return torch.from_numpy(words.copy()).to(dev)
+    if (isinstance(after, torch.Tensor) and after.dtype in (torch.float64, torch.int64) and tuple(after.shape) == (n, 2)
+            and after.is_contiguous() and after.device == dev):
+        return after.view(torch.int64)
+    raise ValueError(f"after must be {n} keys: a pair (t, slot), a HIT_KEY_DTYPE array or contiguous [n, 2] rows on {dev}")
+
+
+def _hits_fn(name):
+    """An entry point of the hit-list feature (a partial RTAMD_HIP_LIB, built from an older source,
+    may lack it)."""
+    try:
+        return getattr(hip_lib(), name)
+    except AttributeError:
+        raise RtError(f"{name}: not exported by this librt_hip.so (RTAMD_HIP_LIB)") from None
 
 
 def _update_fn(name):

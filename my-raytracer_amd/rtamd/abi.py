@@ -37,6 +37,8 @@ RT_AO_MAX_POINTS = 1 << 31
 RT_CAMERA_ROW_MAJOR = 0
 RT_CAMERA_TILE_MAJOR = 1
 RT_CAMERA_MAX_PIXELS = 1 << 31
+RT_HITS_MAX_K = 8
+RT_HITS_MAX_ROWS = 1 << 31
 RT_MULTI_GATHER = 0
 RT_MULTI_PEER = 1
 RT_MULTI_DEBUG_PEER_MISMATCH = 1
@@ -158,6 +160,11 @@ class Hit(C.Structure):
                 ("slot", C.c_int), ("mesh", C.c_int), ("prim", C.c_int), ("reserved_", C.c_int)]
 
 
+class HitKey(C.Structure):
+    """rt_hit_key: the (t, slot) a hit list resumes after (rt_trace_hits); rtamd.HIT_KEY_DTYPE is its numpy row."""
+    _fields_ = [("t", C.c_double), ("slot", C.c_int), ("reserved_", C.c_int)]
+
+
 class QueryStats(C.Structure):
     _fields_ = [("rays", C.c_longlong), ("hits", C.c_longlong), ("stack_spills", C.c_longlong),
                 ("watchdog", C.c_longlong), ("reserved_", C.c_longlong * 4)]
@@ -262,6 +269,8 @@ HIP_SYMBOLS = {
                                    C.c_void_p]),
     "rt_trace_occluded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.POINTER(QueryStats),
                                     C.c_void_p]),
+    "rt_trace_hits": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                C.POINTER(QueryStats), C.c_void_p]),
     "rt_trace_radiance": (C.c_int, [C.c_void_p, C.POINTER(RenderParams), C.c_void_p, C.c_longlong, C.c_void_p,
                                     C.POINTER(Stats), C.c_void_p]),
     "rt_scene_bounds": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
